@@ -1,6 +1,6 @@
 """Headline benchmark: 2-hop MATCH count(*) on R-MAT scale 24 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scale 24]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scale 24] [--dump-outputs DIR] [--full]
 
 One step = one execution of
     MATCH (a)-->(b)-->(c) RETURN count(*)
@@ -11,7 +11,13 @@ generated on the device before the timed region (inputs resident in HBM).
 
 value = joined rows/s = count(*) (path multiplicity) / median step time, whole
 job: the K timed steps are K single queries, each from the plan call to the
-scalar on the host; the pipelined serving rate is a side field.
+scalar on the host.
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds what takes runs of its own: the pipelined serving rate (a side
+field), the profiled pass behind the per-kernel roofline figures and the CPU
+baseline.  --dump-outputs DIR writes what the last timed step returned as
+DIR/<name>.npy (float64), for output-by-output comparison of two builds.
 For N > 1 the graph is hash-partitioned over one process per GPU (dist.py);
 ranks are launched by torch.distributed.run, and the max over ranks is timed.
 """
@@ -394,6 +400,46 @@ def timed_steps(fn, steps, sync):
     return out, time.perf_counter() - t0
 
 
+DUMP_CAP_BYTES = 60_000_000  # --dump-outputs: all files of one run together stay under 64 MB
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: what the last timed step returned, one float64
+    DIR/<name>.npy per array.  Arrays that would not fit DUMP_CAP_BYTES
+    together are cut to a fixed, seeded sample of their elements (the same
+    positions for equally long arrays, so the columns of a table stay aligned)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64).reshape(-1) for k, v in arrays.items()}
+    budget = DUMP_CAP_BYTES // (8 * max(1, len(arrays)))  # elements per array
+    picks = {}
+    for name, a in arrays.items():
+        if a.size > budget:
+            if a.size not in picks:
+                picks[a.size] = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, budget, replace=False))
+            a = a[picks[a.size]]
+        safe = "".join(ch if ch.isalnum() or ch in "_.-" else "_" for ch in name)  # column names hold ':'
+        np.save(os.path.join(out_dir, safe + ".npy"), a)
+
+
+def table_outputs(table):
+    """The columns of a materialised result table as host arrays (NULLs as
+    NaN), rows in sorted order: the joins emit rows in no fixed order."""
+    import numpy as np
+    cols = list(table.physicalColumns)
+    data = []
+    for c in cols:
+        vals, valid = table.column_arrays(c)
+        vals = np.asarray(vals, dtype=np.float64)
+        vals[~valid] = np.nan
+        data.append(vals)
+    if data:
+        order = np.lexsort(data[::-1])
+        data = [d[order] for d in data]
+    return dict(zip(cols, data))
+
+
 def run_rows_leg(args):
     """Materialising join leg: K steps of plan + evaluation of
     MATCH (a)-->(b) RETURN a, b into device memory (no download), ids FOR32.
@@ -421,20 +467,28 @@ def run_rows_leg(args):
         step()
     s.sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    out = None
+    for i in range(args.steps):
+        if args.dump_outputs and i == args.steps - 1:
+            out = step()  # only the last step's table is kept
+        else:
+            step()
     s.sync()
     elapsed = time.perf_counter() - t0
-    s.reset_profile()
-    s.set_profiling(True)
-    prof_steps = max(1, min(args.steps, 5))
-    for _ in range(prof_steps):
-        step()
-    s.sync()
-    s.set_profiling(False)
-    prof = s.profile()
-    per = {k: v["total_ms"] / prof_steps for k, v in prof.items()}
-    kern_ms = sum(per.values())
+    if args.dump_outputs and out is not None:
+        dump_outputs(args.dump_outputs, table_outputs(out))
+    prof, per, kern_ms, prof_steps = {}, {}, None, 0
+    if args.full:  # a second, profiled pass: the timed kernels' split
+        s.reset_profile()
+        s.set_profiling(True)
+        prof_steps = max(1, min(args.steps, 5))
+        for _ in range(prof_steps):
+            step()
+        s.sync()
+        s.set_profiling(False)
+        prof = s.profile()
+        per = {k: v["total_ms"] / prof_steps for k, v in prof.items()}
+        kern_ms = sum(per.values())
     # var2: both rel scans are read (the path step and its start/target joins)
     compulsory = (32.0 if var2 else 16.0) * m + 16.0 * n_nodes + 18.0 * rows
     ms = elapsed * 1e3 / args.steps
@@ -467,7 +521,9 @@ def run_rows_leg(args):
         # the step runs many small kernels (two joins, gathers, scans): the
         # roofline is taken over the whole step's wall time; the timed
         # kernels' split (partition / join passes) is reported beside it
-        "roofline": ({"bound": "hbm", "kernel": "whole step (2 joins + gathers + scans), wall time",
+        # (--full: whether any kernel ran is known from the profiled pass only)
+        "roofline": (None if kern_ms is None else
+                     {"bound": "hbm", "kernel": "whole step (2 joins + gathers + scans), wall time",
                       "achieved": compulsory / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                       "frac": compulsory / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                       "traffic": traffic, "traffic_scope": "hidx_probe launches of one step" if traffic else None,
@@ -560,6 +616,28 @@ def run_reach_leg(args):
         if hist != want:
             raise SystemExit("config 5 histogram differs from the committed fixture")
         parity = {"fixture": "tests/golden/config5_sf10.json", "match": True, "histogram_rows": len(want)}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"reach": [r for r, _ in hist], "n": [c for _, c in hist]})
+    result = {
+        "metric": REACH_METRIC, "value": pairs / (median_ms * 1e-3), "unit": "distinct (a, b) pairs/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": median_ms,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "int64",
+        "data": (f"synthetic LDBC-SF10-shaped graph: R-MAT s{args.scale} (Graph500 a/b/c), edge factor "
+                 f"{args.edge_factor}, every node a Person, generated in HBM before timing"),
+        "config": {"workload": workload_name(args), "scale": args.scale, "nodes": n, "rels": m,
+                   "distinct_pairs": pairs, "sources_reaching": sum(c for _, c in hist),
+                   "plan": ("relational plan through the Table SPI; Group(a; count) over Distinct(a, b) over the "
+                            "UNION ALL of the *1..3 join chains recognised in the runtime DAG → fused "
+                            "var-length reach (try_fused_reach)"),
+                   "steps_mode": "K single queries, plan call -> histogram rows on the host; value = pairs / median",
+                   "ms_per_query_mean": sum(times) * 1e3 / len(times), "ms_per_query_min": min(times) * 1e3,
+                   "first_query_ms": first_ms, "parity": parity},
+        "roofline": None,
+    }
+    if not args.full:
+        print(json.dumps(result))
+        return
+    # --full: a second, profiled pass attributes the device time to the kernels
     s.reset_profile()
     s.set_profiling(True)
     prof_steps = max(1, min(args.steps, 5))
@@ -587,21 +665,7 @@ def run_reach_leg(args):
         nq = max(1, ks.get("k_vr_count_bs", {}).get("dispatches", 1))
         inter = sum(v["write_bytes"] * (v["dispatches"] / nq) for k, v in ks.items()
                     if v["dispatches"] >= nq)  # per-query kernels (the cached index is built once)
-    result = {
-        "metric": REACH_METRIC, "value": pairs / (median_ms * 1e-3), "unit": "distinct (a, b) pairs/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": median_ms,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "int64",
-        "data": (f"synthetic LDBC-SF10-shaped graph: R-MAT s{args.scale} (Graph500 a/b/c), edge factor "
-                 f"{args.edge_factor}, every node a Person, generated in HBM before timing"),
-        "config": {"workload": workload_name(args), "scale": args.scale, "nodes": n, "rels": m,
-                   "distinct_pairs": pairs, "sources_reaching": sum(c for _, c in hist),
-                   "plan": ("relational plan through the Table SPI; Group(a; count) over Distinct(a, b) over the "
-                            "UNION ALL of the *1..3 join chains recognised in the runtime DAG → fused "
-                            "var-length reach (try_fused_reach)"),
-                   "steps_mode": "K single queries, plan call -> histogram rows on the host; value = pairs / median",
-                   "ms_per_query_mean": sum(times) * 1e3 / len(times), "ms_per_query_min": min(times) * 1e3,
-                   "first_query_ms": first_ms, "parity": parity},
-        "roofline": {
+    result["roofline"] = {
             "bound": "hbm", "kernel": "vr_level (pull BFS level, 64 sources per uint64 word)",
             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": achieved / HBM_PEAK_GBS if achieved else None, "traffic": traffic,
@@ -616,8 +680,7 @@ def run_reach_leg(args):
                                                      "frontier / visited words, counts); the relational plan "
                                                      "would materialise every path row (≈1e10 x 40 B)"),
             "kernel_ms": lev_ms, "kernel_ms_per_query": per, "device_ms_per_query": sum(per.values()),
-            "traffic_source": pmc_prov},
-    }
+            "traffic_source": pmc_prov}
     if not args.no_cpu:
         src, _ = rels.column_arrays("source")
         dst, _ = rels.column_arrays("target")
@@ -650,8 +713,10 @@ def run_single(args):
     # and ms_per_step come from their MEDIAN
     count, times = timed_singles(step, args.steps, s.sync)
     median_ms = statistics.median(times) * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"count": [count]})
     pipelined_ms = None
-    if not args.sync_steps and args.query != "triangle":
+    if args.full and not args.sync_steps and args.query != "triangle":
         # side figure (not the value): pipelined serving — step i plans query i
         # on the host and enqueues its fused count into slot i
         # (capf_table_count_async) while the GPU still runs query i−1; every
@@ -677,43 +742,57 @@ def run_single(args):
         got = slots.cpu().tolist()
         if any(c != count for c in got):
             raise SystemExit(f"pipelined counts {got} differ from the synchronous count {count}")
-    # a second, profiled pass attributes the device time to the kernels
-    s.reset_profile()
-    s.set_profiling(True)
-    prof_steps = max(1, min(args.steps, 5))
-    timed_steps(step, prof_steps, s.sync)
-    s.set_profiling(False)
-    prof = s.profile()
+    prof, prof_steps = {}, 0
+    if args.full:
+        # a second, profiled pass attributes the device time to the kernels
+        s.reset_profile()
+        s.set_profiling(True)
+        prof_steps = max(1, min(args.steps, 5))
+        timed_steps(step, prof_steps, s.sync)
+        s.set_profiling(False)
+        prof = s.profile()
     plan = s.last_plan()
     # src+dst at int64 width + node ids (+ the 1-B label for config 2)
     compulsory = 16.0 * m + (9.0 if args.query == "one_hop_person" else 8.0) * n_nodes
-    traffic = None
-    pfx = {"triangle": "tri_", "one_hop_person": "c2_"}.get(args.query, "")
-    pmc = os.path.join(ROOT, "profiles", f"pmc_{pfx}s{args.scale}.json")
-    ran = sorted(k for k, v in prof.items() if k in PIPELINE and v["total_ms"] > 0)
-    if args.query == "triangle":  # the count kernels (the CSR is built by the first query)
-        ran = [k for k in ran if k.startswith("tri_count")]
-    j, pmc_prov = load_pmc(pmc, ran)
-    if j is not None:
-        traffic = pmc_bytes_of(j, ran) if args.query == "triangle" else j.get("hbm_bytes_per_query")
     ms_per_step = median_ms
-    if args.query == "triangle":
-        roof = tri_roofline(prof, prof_steps, n_nodes, traffic)
+    if args.full:
+        traffic = None
+        pfx = {"triangle": "tri_", "one_hop_person": "c2_"}.get(args.query, "")
+        pmc = os.path.join(ROOT, "profiles", f"pmc_{pfx}s{args.scale}.json")
+        ran = sorted(k for k, v in prof.items() if k in PIPELINE and v["total_ms"] > 0)
+        if args.query == "triangle":  # the count kernels (the CSR is built by the first query)
+            ran = [k for k in ran if k.startswith("tri_count")]
+        j, pmc_prov = load_pmc(pmc, ran)
+        if j is not None:
+            traffic = pmc_bytes_of(j, ran) if args.query == "triangle" else j.get("hbm_bytes_per_query")
+        if args.query == "triangle":
+            roof = tri_roofline(prof, prof_steps, n_nodes, traffic)
+        else:
+            roof = pipeline_roofline(prof, prof_steps, compulsory, traffic)
+            # `achieved` / `frac` on the basis the driver's clock and
+            # rocprof reproduce — the compulsory bytes over the median plan -> scalar
+            # step (host planning included, so it is the conservative figure); the
+            # HIP-event kernel sum of the profiled pass is kept beside it (events
+            # between the kernels move P1's dirty-line write-back out of the timed
+            # spans, so that sum reads ~5 % below the rocprof kernel-trace sum)
+            roof["kernel_event_achieved"] = roof["achieved"]
+            roof["kernel_event_frac"] = roof["frac"]
+            roof["achieved"] = compulsory / (ms_per_step * 1e-3) / 1e9
+            roof["frac"] = roof["achieved"] / HBM_PEAK_GBS
+            roof["basis"] = "compulsory bytes / median plan->scalar ms_per_step (kernel-event figures: kernel_event_*)"
+            roof["end_to_end_frac"] = roof["frac"]
+        roof["traffic_source"] = pmc_prov
+    elif args.query == "triangle":  # its roofline is the count kernels' probe traffic: profiled pass only
+        roof = None
     else:
-        roof = pipeline_roofline(prof, prof_steps, compulsory, traffic)
-        # `achieved` / `frac` on the basis the driver's clock and
-        # rocprof reproduce — the compulsory bytes over the median plan -> scalar
-        # step (host planning included, so it is the conservative figure); the
-        # HIP-event kernel sum of the profiled pass is kept beside it (events
-        # between the kernels move P1's dirty-line write-back out of the timed
-        # spans, so that sum reads ~5 % below the rocprof kernel-trace sum)
-        roof["kernel_event_achieved"] = roof["achieved"]
-        roof["kernel_event_frac"] = roof["frac"]
-        roof["achieved"] = compulsory / (ms_per_step * 1e-3) / 1e9
-        roof["frac"] = roof["achieved"] / HBM_PEAK_GBS
-        roof["basis"] = "compulsory bytes / median plan->scalar ms_per_step (kernel-event figures: kernel_event_*)"
-        roof["end_to_end_frac"] = roof["frac"]
-    roof["traffic_source"] = pmc_prov
+        # the end-to-end figure needs no run of its own: the compulsory bytes
+        # over the median timed step (the kernel split is --full's)
+        achieved = compulsory / (ms_per_step * 1e-3) / 1e9
+        roof = {"bound": "hbm", "kernel": "fused count pipeline, whole plan->scalar step", "achieved": achieved,
+                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                "algorithmic_bytes_per_launch": compulsory,
+                "basis": "compulsory bytes / median plan->scalar ms_per_step",
+                "end_to_end_frac": achieved / HBM_PEAK_GBS}
     result = {
         "metric": {"two_hop": METRIC, "triangle": TRI_METRIC, "one_hop_person": ONE_HOP_METRIC}[args.query],
         "value": count / (median_ms * 1e-3),
@@ -750,6 +829,9 @@ def run_single(args):
         result["config"]["p3_handoffs_per_query"] = prof["c3_handoffs"]["bytes"] / prof_steps
     result["config"]["parity"] = check_fixture(args, count)
     result["config"]["lib"] = lib_digest()
+    if not args.full:
+        print(json.dumps(result))
+        return
     if not args.no_cpu and args.query == "two_hop":
         result["cpu_baseline"] = cpu_baseline(s, g, args.scale, args.cpu_seconds)
     if not args.no_cpu and args.query == "triangle":
@@ -872,7 +954,9 @@ def run_distributed(args):
     median_ms = statistics.median(step_max) * 1e3
     parity = check_fixture(args, count)
     pipelined_ms = None
-    if pipe is not None and not args.sync_steps:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"count": [count]})
+    if args.full and pipe is not None and not args.sync_steps:
         # side figure: pipelined serving — local partial + all-reduce into slot
         # i without a host read (step i's all-reduce overlaps step i+1's
         # kernels); the K counts are checked after the closing synchronize
@@ -893,20 +977,22 @@ def run_distributed(args):
         got = slots.cpu().tolist()
         if any(c != count for c in got):
             raise SystemExit(f"rank {rank}: pipelined counts {got} differ from {count}")
-    s.reset_profile()
-    s.set_profiling(True)
-    prof_steps = max(1, min(args.steps, 5))
-    for _ in range(prof_steps):
-        step()
-    torch.cuda.synchronize()
-    s.set_profiling(False)
-    prof = s.profile()
-    # every rank's device time per query; the JSON reports the slowest rank's
-    rank_ms = sum(v["total_ms"] for k, v in prof.items() if k in PIPELINE) / prof_steps
-    per_rank = torch.zeros(world, dtype=torch.float64, device="cuda")
-    per_rank[rank] = rank_ms
-    dist.all_reduce(per_rank, op=dist.ReduceOp.SUM)
-    per_rank = per_rank.cpu().tolist()
+    prof, prof_steps, per_rank = {}, 0, None
+    if args.full:  # a profiled pass: the device time of the kernels, rank by rank
+        s.reset_profile()
+        s.set_profiling(True)
+        prof_steps = max(1, min(args.steps, 5))
+        for _ in range(prof_steps):
+            step()
+        torch.cuda.synchronize()
+        s.set_profiling(False)
+        prof = s.profile()
+        # every rank's device time per query; the JSON reports the slowest rank's
+        rank_ms = sum(v["total_ms"] for k, v in prof.items() if k in PIPELINE) / prof_steps
+        per_rank = torch.zeros(world, dtype=torch.float64, device="cuda")
+        per_rank[rank] = rank_ms
+        dist.all_reduce(per_rank, op=dist.ReduceOp.SUM)
+        per_rank = per_rank.cpu().tolist()
     sys.stdout.flush()
     os.dup2(json_fd, 1)
     if rank == 0:
@@ -938,10 +1024,10 @@ def run_distributed(args):
                 "ms_per_step_pipelined": pipelined_ms,
                 "parity": parity,
                 "device_ms_per_query_by_rank": per_rank,
-                "max_rank_device_ms": max(per_rank),
+                "max_rank_device_ms": max(per_rank) if per_rank else None,
                 "one_device_rehearsal": bool(args.one_device),
             },
-            "roofline": pipeline_roofline(prof, prof_steps, compulsory),
+            "roofline": pipeline_roofline(prof, prof_steps, compulsory) if args.full else None,
         }))
     dist.destroy_process_group()
 
@@ -1002,8 +1088,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scale", type=int, default=None, help="R-MAT scale (default 24; 16 for --query reach)")
     ap.add_argument("--edge-factor", type=int, default=None, help="default 16; 30 for --query reach")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the pipelined side figure, the profiled pass "
+                         "(per-kernel and roofline figures, PMC traffic) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: probe budget of the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--sync-steps", action="store_true",
                     help="time query-at-a-time steps only (result downloaded every step)")
     ap.add_argument("--int64", action="store_true", help="keep the id columns int64 (no FOR encoding)")

@@ -1,5 +1,5 @@
-"""One line per bench JSON (not a test): file, median plan->scalar ms, pipelined
-ms, per-kernel ms."""
+"""One line per bench JSON of a `bench.py --full` run (not a test): file, median
+plan->scalar ms, pipelined ms, per-kernel ms."""
 import json
 import sys
 

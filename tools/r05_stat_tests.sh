@@ -8,4 +8,5 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method threa
 rc=$?
 tail -5 gpurun_out/r05_stat.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 300 python -u bench.py > gpurun_out/r05_base_bench.json 2> gpurun_out/r05_base_bench.err
+mkdir -p bench_out
+timeout -k 10 300 python -u bench.py --full > bench_out/r05_base_bench.json 2> bench_out/r05_base_bench.err

@@ -5,5 +5,6 @@ bash tools/gpu_tests.sh r06_tail tests/test_jni_exec.py tests/test_ldbc_config5.
 rc=$?
 echo "tail rc=$rc"
 case $rc in 124|134|137|139) exit $rc;; esac
-timeout -k 10 300 python -u bench.py > gpurun_out/r06_bench2.json 2> gpurun_out/r06_bench2.err || exit $?
-python3 -c "import json;d=json.load(open('gpurun_out/r06_bench2.json'));r=d['roofline'];print(d['ms_per_step'], r['frac'], r['kernel_event_frac'], d['config']['ms_per_step_pipelined'])"
+mkdir -p bench_out
+timeout -k 10 300 python -u bench.py --full > bench_out/r06_bench2.json 2> bench_out/r06_bench2.err || exit $?
+python3 -c "import json;d=json.load(open('bench_out/r06_bench2.json'));r=d['roofline'];print(d['ms_per_step'], r['frac'], r['kernel_event_frac'], d['config']['ms_per_step_pipelined'])"

@@ -6,7 +6,8 @@ rc=$?
 echo "tail rc=$rc"
 case $rc in 124|134|137|139) exit $rc;; esac
 for w in 6 7 8; do
-  CAPF_TRI_WPE=$w timeout -k 10 300 python bench.py --query triangle --scale 24 --steps 5 --warmup 1 --no-cpu \
-    > gpurun_out/r06_tri_wpe$w.json 2> gpurun_out/r06_tri_wpe$w.err || exit $?
-  python3 -c "import json;d=json.load(open('gpurun_out/r06_tri_wpe$w.json'));r=d['roofline'];print('wpe $w', d['ms_per_step'], r['kernel_ms_per_query'], r['frac'], d['config']['parity'])"
+  mkdir -p bench_out
+  CAPF_TRI_WPE=$w timeout -k 10 300 python bench.py --full --query triangle --scale 24 --steps 5 --warmup 1 --no-cpu \
+    > bench_out/r06_tri_wpe$w.json 2> bench_out/r06_tri_wpe$w.err || exit $?
+  python3 -c "import json;d=json.load(open('bench_out/r06_tri_wpe$w.json'));r=d['roofline'];print('wpe $w', d['ms_per_step'], r['kernel_ms_per_query'], r['frac'], d['config']['parity'])"
 done
