@@ -18,21 +18,27 @@
 //         8-key-padded run sizes, LDS counting sort of the keys (uint16 =
 //         h & 0xFFFF) into a stage prefilled with pad keys, ONE contiguous
 //         copy-out into the tile's region, one (start/8 | count << 16) word
-//         per run; self-loop term on the side
-//   T  k_c3_transpose  [tile][run] → [run][tile] meta, per-run totals
+//         per run, run-major ([run][tile]) in the default pipeline; per-tile
+//         self-loop count on the side; clears the post-P1 work area
+//   P3 k_c5_gather     per unit (by default: one exclusive unit per run, no
+//         work list): 64 Ki counters as packed uint16 pairs in 128 KiB LDS;
+//         each wave flattens the segments of 64 tiles into one sequence of
+//         16-B pieces (coalesced 128-B lines, every lane live, no per-key
+//         predicate: pads are counted and subtracted), flushes every bin with
+//         plain stores (no memset anywhere); a counter reaching 2^15 hands
+//         that much off to a log (rare)
+//   D  k_chain2_dot_pairs  Σ in·out + the log's terms + self-loops (fused_count.hip)
+// That is the default at ≥ 256 runs (s24).  The other modes of the fused count
+// (C5PostPlan; the table of all six is in DESIGN.md) add
+//   T  k_c3_transpose  [tile][run] → [run][tile] meta, per-run totals, Σ self-loops
 //   U  k_c3_units      device work list (one unit per run; hub-heavy runs split)
-//   P3 k_c5_gather     per unit: 64 Ki counters as packed uint16 pairs in
-//         128 KiB LDS; each wave flattens the segments of 64 tiles into one
-//         sequence of 16-B pieces (coalesced 128-B lines, every lane live, no
-//         per-key predicate: pads are counted and subtracted), flushes every
-//         bin with plain stores (no memset anywhere)
-//   O  k_c3_overflow   adds the 2^15 carries a uint16 counter hands off (rare)
-//   D  k_chain2_dot    Σ in·out (fused_count.hip)
+//   O  k_c3_overflow   adds the logged hand-offs to the histograms
+// and a node-partitioned rank (chain2_sharded) has its own P1 and a static work list.
 // Bytes per rel at FOR32 width: P1 8 read + 4(+pads) written, P3 4(+pads) read.
 // Both big kernels are VALU-issue bound before they are HBM bound (PMC:
 // SQ_INSTS_VALU), so the per-key instruction count is what the code minimises.
 #include <algorithm>
-#include <cstdio>
+#include <cassert>
 #include <cstring>
 #include <type_traits>
 #include <vector>
@@ -407,7 +413,7 @@ constexpr int C3_TT = 256;
 // self-loop counts (P1's per-tile plain stores) into *loops.
 __device__ __forceinline__ void c3_transpose_body(uint32_t (*tilebuf)[33], const uint32_t *meta,
                                                   uint32_t *meta_t, int64_t ntiles, int nr,
-                                                  unsigned long long *run_total, int64_t tt, uint32_t *bsum,
+                                                  unsigned long long *run_total, int64_t tt,
                                                   const uint32_t *tile_loops, unsigned long long *loops) {
   __shared__ uint32_t part[8][33];
   const int r0 = blockIdx.y * 32;
@@ -435,8 +441,6 @@ __device__ __forceinline__ void c3_transpose_body(uint32_t (*tilebuf)[33], const
 #pragma unroll
     for (int q = 0; q < 8; ++q) c += part[q][tx];
     if (c && r < nr) atomicAdd(&run_total[r], (unsigned long long)c);
-    // per-(run, tile block) key counts: the balanced P3's split points
-    if (bsum && r < nr) bsum[(int64_t)r * gridDim.x + blockIdx.x] = c;
   }
   if (!meta_t) return;  // run totals only (P3 reads meta in place)
   const int lt = __builtin_ctzll((unsigned long long)tt);  // tt is a power of two
@@ -448,11 +452,9 @@ __device__ __forceinline__ void c3_transpose_body(uint32_t (*tilebuf)[33], const
 __global__ __launch_bounds__(256) void k_c3_transpose(const uint32_t *meta, uint32_t *meta_t,
                                                        int64_t ntiles, int nr,
                                                        unsigned long long *run_total, int64_t tt,
-                                                       uint32_t *bsum = nullptr,
-                                                       const uint32_t *tile_loops = nullptr,
-                                                       unsigned long long *loops = nullptr) {
+                                                       const uint32_t *tile_loops, unsigned long long *loops) {
   __shared__ uint32_t tilebuf[C3_TT][33];
-  c3_transpose_body(tilebuf, meta, meta_t, ntiles, nr, run_total, tt, bsum, tile_loops, loops);
+  c3_transpose_body(tilebuf, meta, meta_t, ntiles, nr, run_total, tt, tile_loops, loops);
 }
 
 struct C3Unit {
@@ -478,9 +480,9 @@ constexpr int C3_UBLOCK = 1024;
 // exclusive one, whose plain stores cover all bins of its bucket: the
 // histograms need no memset, empty runs included (they store zeros).  A run
 // holding more than twice the mean (a hub-heavy bucket) is split into tile
-// ranges that flush with atomic adds into bins cleared by k_c3_zero.  Units
-// stay in run order: P3 maps them onto XCDs in groups of consecutive runs
-// (c3_unit_of).
+// ranges that flush with atomic adds into bins that the first of them to
+// start clears (claim / ready bits in P3).  Units stay in run order: P3 maps
+// them onto XCDs in groups of consecutive runs (c3_unit_of).
 struct C3Sides {
   int nb;              // runs per side: runs [0, nb) in, [nb, 2·nb) out
   int64_t t0[2], t1[2];  // tile range holding each side's segments
@@ -493,7 +495,7 @@ struct C3Sides {
                        // pairs in the first half of their bucket's 2^16 words (half
                        // the flush and dot bytes); split runs keep one uint32 per bin
   int32_t *claim = nullptr;  // the units kernel's split flags: non-null → P3's split units
-                             // clear their own buckets (claim / ready bits, no k_c3_zero)
+                             // clear their own buckets (claim / ready bits)
 };
 
 // CAPF_P3_SPLIT (tuning): split threshold in units of the mean run size
@@ -501,16 +503,6 @@ static int c3_split_x16() {
   const char *e = getenv("CAPF_P3_SPLIT");
   return e ? std::max(1, (int)(16.0 * atof(e))) : 32;
 }
-
-// The P1 → P3 path of the fused 2-hop count: P1's per-tile self-loops (summed
-// into acc3[1] by the transpose), acc3 = [Σ in·out, self-loops, done] cleared
-// by P1's tile-0 workgroup, and where the hand-off log goes.
-struct C3Post {
-  const uint32_t *tile_loops;
-  int64_t ntiles;
-  unsigned long long *acc3;
-  C2Spill *spill;  // host side: non-null → the hand-off log goes to the dot kernel
-};
 
 // The work-list computation (one workgroup, RPT runs per thread, nr ≤
 // RPT·blockDim.x).  (Per-(run, block) partial rows stored by the transpose
@@ -686,7 +678,7 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
   // zero: the first unit of (run, slice) to start sets its claim bit and clears
   // the bucket in HBM, then its ready bit; the others wait for the ready bit
   // before flushing.  A waiter only ever waits on a workgroup already running
-  // (the claimer), so the wait ends — and k_c3_zero plus a kernel boundary go.
+  // (the claimer), so the wait ends — no clearing kernel, no kernel boundary.
   const bool zsplit = sd.claim && !u.exclusive;
   if (zsplit) {
     __shared__ int zown;
@@ -957,129 +949,210 @@ static void launch_c5(Session *s, const C5Cols<W> &c, uint16_t *part, uint32_t *
   }
 }
 
-// Everything after P1: meta transpose + run totals, the work list, P3, the
-// overflow hand-offs.  `part`/`meta` hold ntiles tiles of nr = 2·sd.nb runs.
-// Histograms: S slices (c5_slices) of sd.nb·64 Ki counters per side, slice s
-// at h_in/h_out + s·slice_stride; every counter of every slice is written.
-// Bytes of c5_post's work area (run totals, counters, split flags, units, the
-// hand-off log) and its leading words that must start at zero.
-static int64_t c5_post_acc_bytes(int nr, int S, int split_x16, int64_t nkeys, int *max_units_out,
-                                 uint32_t *ovf_cap_out) {
+// ------------------------------------------------------------- after P1
+// c5_post runs everything between P1 and the dot: (meta transpose + run
+// totals, the work list,) P3 and (the overflow hand-offs).  What it launches is
+// a C5PostPlan, built by c5_plan_fused or c5_plan_sharded and by nothing else.
+
+// Work area of the post-P1 kernels: run_total[nr] (uint64) | counters (4 ×
+// int32: [0] units, [1] hand-off events) | hand-off log | split[nr] | units.
+// Byte offsets; the first `zero_bytes` must start at zero — the run totals and
+// counters are added to, a reserved log slot may be read before its owner
+// wrote it (a zero entry adds nothing), and the split flags are read by the
+// dot when no work-list kernel wrote them.
+struct C5PostLayout {
+  int max_units;     // capacity of the work list (whole XCD waves)
+  uint32_t ovf_cap;  // capacity of the hand-off log
+  int64_t run_total, counters, log, split, units, bytes, zero_bytes;
+};
+
+static C5PostLayout c5_post_layout(int nr, int S, int split_x16, int64_t nkeys) {
+  C5PostLayout l;
   // runs × slices + hub splits (≤ 2 per run beyond the slices), whole XCD waves
   // Σ_runs max(S, ⌈cnt/target⌉) ≤ S·nr + nr + total/target, target ≥ split/16 × mean
-  const int max_units = (S * nr + nr + 16 * nr / std::max(1, split_x16) + 2 + 255) / 256 * 256;
+  l.max_units = (S * nr + nr + 16 * nr / std::max(1, split_x16) + 2 + 255) / 256 * 256;
   // every overflow event consumes 2^15 adds of one half-counter within one unit
-  const uint32_t ovf_cap = (uint32_t)(nkeys / (1 << 15) + 64 + 16 * (int64_t)max_units);
-  if (max_units_out) *max_units_out = max_units;
-  if (ovf_cap_out) *ovf_cap_out = ovf_cap;
-  // run_total[nr] | nunits[4] | bdone[nr] | hand-off log | split[nr] | rnu[nr] | units
-  return 8 * nr + 16 + 12 * nr + (int64_t)sizeof(C3Unit) * max_units + 8 * (int64_t)ovf_cap;
-}
-// words that start at zero: run totals, unit / event / done counters, bucket counters
-// (and the hand-off log: P3's bucket-dot epilogue may read a reserved slot
-// that another bucket's unit has not written yet — a zero entry adds nothing)
-static int64_t c5_post_zero_words(int nr, uint32_t ovf_cap, bool with_split = false) {
-  return (8 * (int64_t)nr + 16 + 4 * (int64_t)nr + 8 * (int64_t)ovf_cap + (with_split ? 4 * (int64_t)nr : 0)) / 4;
+  l.ovf_cap = (uint32_t)(nkeys / (1 << 15) + 64 + 16 * (int64_t)l.max_units);
+  l.run_total = 0;
+  l.counters = l.run_total + 8 * (int64_t)nr;
+  l.log = l.counters + 16;
+  l.split = l.log + 8 * (int64_t)l.ovf_cap;
+  l.units = l.split + 4 * (int64_t)nr;  // nr = 2·nb is even: 8-B aligned like the log
+  l.bytes = l.units + (int64_t)sizeof(C3Unit) * l.max_units;
+  l.zero_bytes = l.units;
+  assert(l.log % 8 == 0 && l.units % 8 == 0);  // uint2 entries, C3Unit's int64 fields
+  return l;
 }
 
-static void c5_post(Session *s, const uint16_t *part, const uint32_t *meta, const C3Sides &sd,
-                    int64_t ntiles, int64_t rstride, int64_t nkeys, int S, uint32_t *h_in,
-                    uint32_t *h_out, int64_t slice_stride, bool static_units = false,
-                    C3Ovf *packed_ovf = nullptr, BufPtr *keep = nullptr, const C3Post *post = nullptr,
-                    BufPtr acc_pre = BufPtr(), bool direct = false) {
-  const int nr = 2 * sd.nb;
+enum class C5Work {
+  Units,   // k_c3_transpose + k_c3_units: a device work list over run-major meta (hub runs split)
+  Direct,  // no list: P1 wrote run-major meta, unit r is run r
+  Static   // no list: unit (run, k) is tile range k of S, P1's tile-major meta read in place
+};
+enum class C5Counters {
+  U32,    // one uint32 per bin
+  Pairs,  // exclusive units: packed uint16 pairs in the first half of the bucket; split runs uint32
+  Packed  // packed uint16 pairs, bucket b of slice k at (k·nb + b)·2^15 words
+};
+enum class C5Log {
+  Overflow,  // k_c3_overflow adds the hand-offs to the histograms
+  Dot,       // left to the fused dot kernel (C2Spill)
+  PackedDot  // left to k_c5_dot_packed
+};
+struct C5Mode {
+  C5Work work;
+  C5Counters counters;
+  C5Log log;
+};
+
+struct C5PostPlan {
+  C5Mode mode;
+  C3Sides sides;  // runs per side, tile ranges, split threshold (+ the counter format, as P3 reads it)
+  int S;          // histogram slices
+  int64_t slice_stride;  // words between the slices of a side
+  int64_t mstride;       // stride of a run's meta words: 1 = run-major, nr = tile-major
+  int64_t ntiles, rstride, nkeys;
+  bool zeroed_by_p1;  // P1's workgroups clear the layout's zero prefix (else: a memset here)
+  C5PostLayout layout;
+};
+
+// part / meta: P1's ntiles tiles of nr = 2·nb runs.  Histograms: S slices per
+// side, slice k at h_in / h_out + k·slice_stride; every counter of every slice
+// is written.  acc: the work area (layout.bytes).  tile_loops / acc3 (fused
+// pipeline only): P1's per-tile self-loops, summed into acc3[1] by the transpose.
+struct C5PostBufs {
+  const uint16_t *part;
+  const uint32_t *meta;
+  uint32_t *h_in, *h_out;
+  BufPtr acc;
+  const uint32_t *tile_loops;
+  unsigned long long *acc3;
+};
+
+// What the dot after c5_post reads: the hand-off log, the split flags (per
+// run: 1 = uint32 bins, 0 = packed pairs) and the work area that holds both.
+struct C5PostOut {
+  C3Ovf ovf;
+  const int32_t *split;
+  BufPtr acc;
+};
+
+// What the two builders share.  Tiles [0, in_end) hold the in side's
+// segments, [out_begin, ntiles) the out side's.
+static C5PostPlan c5_plan(C5Mode m, int nb, int64_t in_end, int64_t out_begin, int64_t ntiles, int64_t rstride,
+                          int64_t nkeys, bool zeroed_by_p1) {
+  const int nr = 2 * nb;
+  C5PostPlan p{};
+  p.mode = m;
+  p.sides = C3Sides{nb, {0, out_begin}, {in_end, ntiles}, c3_split_x16(), m.counters == C5Counters::Packed,
+                    m.counters == C5Counters::Pairs, nullptr};
+  p.S = c5_slices(nr);
+  p.slice_stride = (int64_t)nb * (m.counters == C5Counters::Packed ? C2_WORDS : C2_BW);
+  p.mstride = m.work == C5Work::Static ? nr : 1;
+  p.ntiles = ntiles;
+  p.rstride = rstride;
+  p.nkeys = nkeys;
+  p.zeroed_by_p1 = zeroed_by_p1;
+  p.layout = c5_post_layout(nr, p.S, p.sides.split_x16, nkeys);
+  return p;
+}
+
+// The fused 2-hop count and capf_chain2_local_hists (to_dot false: the caller
+// reads the histograms, no dot kernel takes the hand-off log): every tile
+// holds both sides' runs; P1 clears the work area's zero prefix.
+static C5PostPlan c5_plan_fused(int nb, int64_t ntiles, int64_t rstride, int64_t nkeys, bool to_dot) {
+  // One slice (≥ 256 runs): no transpose and no work-list kernel — P1 writes
+  // run-major meta, every run is one exclusive P3 unit (hash-partitioned runs
+  // are near-uniform: no hub split at s24), the dot adds the self-loops.  s24
+  // (profiles/r05_ab_direct.txt): pipeline 1.000 → 0.980 ms, T 37 + U 8 µs
+  // gone, P1 +8 µs (scattered meta lines), P3 +13 µs (it now pays P1's dirty-line
+  // write-back that T used to).  CAPF_C5_DIRECT=0 keeps the transpose pipeline.
+  const char *de = getenv("CAPF_C5_DIRECT");
+  const bool direct_env = !(de && atoi(de) == 0), one_slice = c5_slices(2 * nb) == 1;
+  const C5Mode m = !to_dot     ? C5Mode{C5Work::Units, C5Counters::U32, C5Log::Overflow}  // D
+                   : !one_slice ? C5Mode{C5Work::Units, C5Counters::U32, C5Log::Dot}      // C: k_c5_fold sums the slices
+                   : direct_env ? C5Mode{C5Work::Direct, C5Counters::Pairs, C5Log::Dot}   // A: the default at ≥ 256 runs
+                                : C5Mode{C5Work::Units, C5Counters::Pairs, C5Log::Dot};   // B
+  return c5_plan(m, nb, ntiles, 0, ntiles, rstride, nkeys, true);
+}
+
+// A node-partitioned rank: tiles [0, t_in) hold the in side, [t_in, ntiles)
+// the out side.  A static work list (S tile ranges per run: a rank's runs hold
+// ≤ 1.4 × the mean at s24, no hub splits happen) needs no run totals, and the
+// rank's few runs (≤ 64 at G = 8) share each tile's meta lines: P3 reads P1's
+// tile-major meta in place, no transpose launch.  Packed uint16 slices (half
+// the slice bytes written by P3 and read by the dot) when several slices per
+// run (G ≥ 4 at s24): with one slice the runs are whole buckets whose hub bins
+// log many hand-offs (measured G = 2: packed dot 41 µs vs uint32 dot + overflow 22 µs).
+static C5PostPlan c5_plan_sharded(int nbl, int64_t t_in, int64_t ntiles, int64_t rstride, int64_t nkeys) {
+  const C5Mode m = c5_slices(2 * nbl) >= 2 ? C5Mode{C5Work::Static, C5Counters::Packed, C5Log::PackedDot}  // F
+                                           : C5Mode{C5Work::Static, C5Counters::U32, C5Log::Overflow};     // E
+  return c5_plan(m, nbl, t_in, t_in, ntiles, rstride, nkeys, false);
+}
+
+static C5PostOut c5_post(Session *s, const C5PostBufs &b, const C5PostPlan &p) {
+  const int nr = 2 * p.sides.nb;
+  const C5PostLayout &l = p.layout;
   static bool attr_set = false;
   if (!attr_set) {
     HIP_CHECK(hipFuncSetAttribute((const void *)k_c5_gather<C5_PPS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   C5_GATHER_LDS));
     attr_set = true;
   }
-  int max_units = 0;
-  uint32_t ovf_cap = 0;
-  const int64_t acc_bytes = c5_post_acc_bytes(nr, S, sd.split_x16, nkeys, &max_units, &ovf_cap);
+  char *base = (char *)b.acc->p;
+  unsigned long long *run_total = (unsigned long long *)(base + l.run_total);
+  int32_t *nunits = (int32_t *)(base + l.counters);
+  int32_t *split = (int32_t *)(base + l.split);
+  C3Unit *units = (C3Unit *)(base + l.units);
+  C5PostOut out{C3Ovf{(uint2 *)(base + l.log), (uint32_t *)(nunits + 1), l.ovf_cap}, split, b.acc};
+  if (!p.zeroed_by_p1) HIP_CHECK(hipMemsetAsync(base, 0, (size_t)l.zero_bytes, s->stream));
+  const bool listed = p.mode.work == C5Work::Units;
   // P3 reads run-major meta (transposed here); reading P1's tile-major meta in
-  // place saved 7 µs of transpose and cost P3 7..20 µs at s24 (measured).  A
-  // node-partitioned rank's static work list needs no run totals, and its few
-  // runs (≤ 64 at G = 8) share each tile's meta lines: P3 reads them in place,
-  // no transpose launch.
-  // direct (2-hop pipeline, one slice): P1 wrote run-major meta and every run is
-  // one exclusive unit — no transpose, no work list; the dot adds the
-  // self-loops and the split flags (all 0) were cleared by P1
-  const bool in_place = (static_units && !post) || direct;
-  BufPtr meta_t = in_place ? BufPtr() : s->alloc(4 * nr * ntiles);
-  // transpose blocks: tiles per block tt, fewer when there are few runs (≥ ~1024 blocks)
-  int64_t tt = C3_TT;
-  // (s24: 128 tiles per block 34 µs, 64 41 µs, 32 54 µs — fewer, longer blocks win;
-  // the same launch again right after takes 19 µs: ~15 µs of T is P1's dirty
-  // lines written back at the boundary, paid by whichever kernel follows P1)
-  while (tt > 32 && ((ntiles + tt - 1) / tt) * ((nr + 31) / 32) < 1024) tt /= 2;
-  const int nparts = (int)((ntiles + tt - 1) / tt);
-  // acc_pre: allocated by the caller, its first c5_post_zero_words words
-  // cleared by P1's tile-0 workgroup (no memset here)
-  BufPtr acc = acc_pre ? acc_pre : s->alloc(acc_bytes);
-  unsigned long long *run_total = (unsigned long long *)acc->p;
-  int32_t *nunits = (int32_t *)(run_total + nr);  // [0] units, [1] overflow events
-  unsigned int *bdone = (unsigned int *)(nunits + 4);  // (reserved: keeps the layout's alignment)
-  uint2 *log = (uint2 *)(bdone + nr);                    // (12·nr + 16 B in: 8-B aligned, nr even)
-  int32_t *split = (int32_t *)(log + ovf_cap);
-  int32_t *rnu = split + nr;
-  C3Unit *units = (C3Unit *)(rnu + nr);
-  C3Ovf ovf{};
-  ovf.n = (uint32_t *)(nunits + 1);
-  ovf.log = log;
-  ovf.cap = ovf_cap;
-  // the hand-off log is folded in by the dot kernel (no overflow kernel) when
-  // the caller takes it
-  const bool log_to_dot = post && post->spill && !sd.packed;
-  if (!acc_pre) HIP_CHECK(hipMemsetAsync(acc->p, 0, 4 * (size_t)c5_post_zero_words(nr, ovf_cap), s->stream));
-  // units in the XCD-grouped run order (largest-first order: measured no gain)
-  const C3UnitsOut uo{units, nunits, split};
-  if (!in_place) {
-    KernelTimer kt(s, "c3_transpose", 8.0 * nr * ntiles);
-    hipLaunchKernelGGL(k_c3_transpose, dim3((unsigned)nparts, (nr + 31) / 32), dim3(256), 0, s->stream, meta,
-                       (uint32_t *)meta_t->p, ntiles, nr, run_total, tt, nullptr,
-                       post ? post->tile_loops : nullptr, post ? post->acc3 + 1 : nullptr);
-    KERNEL_CHECK();
-  }
-  C3Sides sdk = sd;  // as launched: split units clear their buckets (claim bits)
-  const bool stat = static_units || direct;
-  if (!stat) {
+  // place saved 7 µs of transpose and cost P3 7..20 µs at s24 (measured).
+  BufPtr meta_t;
+  C3Sides sdk = p.sides;  // as launched: split units clear their buckets (claim bits)
+  if (listed) {
+    meta_t = s->alloc(4 * nr * p.ntiles);
+    // transpose blocks: tiles per block tt, fewer when there are few runs (≥ ~1024 blocks)
+    // (s24: 128 tiles per block 34 µs, 64 41 µs, 32 54 µs — fewer, longer blocks win;
+    // the same launch again right after takes 19 µs: ~15 µs of T is P1's dirty
+    // lines written back at the boundary, paid by whichever kernel follows P1)
+    int64_t tt = C3_TT;
+    while (tt > 32 && ((p.ntiles + tt - 1) / tt) * ((nr + 31) / 32) < 1024) tt /= 2;
+    const int nparts = (int)((p.ntiles + tt - 1) / tt);
+    {
+      KernelTimer kt(s, "c3_transpose", 8.0 * nr * p.ntiles);
+      hipLaunchKernelGGL(k_c3_transpose, dim3((unsigned)nparts, (nr + 31) / 32), dim3(256), 0, s->stream, b.meta,
+                         (uint32_t *)meta_t->p, p.ntiles, nr, run_total, tt, b.tile_loops, b.acc3 + 1);
+      KERNEL_CHECK();
+    }
     sdk.claim = split;
     // the work list in its own one-workgroup kernel (fusing it into the
     // transpose's last workgroup made T+U 55 µs against 35 + 6 µs + a 10 µs
-    // boundary at s24)
+    // boundary at s24); units in the XCD-grouped run order (largest-first
+    // order: measured no gain)
     KernelTimer kt(s, "c3_units", 8.0 * nr);
-    hipLaunchKernelGGL(k_c3_units, dim3(1), dim3(C3_UBLOCK), 0, s->stream, run_total, nr, sd, S, uo);
+    hipLaunchKernelGGL(k_c3_units, dim3(1), dim3(C3_UBLOCK), 0, s->stream, run_total, nr, p.sides, p.S,
+                       C3UnitsOut{units, nunits, split});
     KERNEL_CHECK();
   }
   {
     // (folding the dot into P3's epilogue measured 0.51 ms for P3 against
     // 0.44 + 0.027 ms + a ~10 µs boundary: the dot kernel runs after P3)
-    KernelTimer kt(s, "c5_gather", 2.0 * nkeys);
-    const int grid = stat ? (nr * S + 255) / 256 * 256 : max_units;
+    KernelTimer kt(s, "c5_gather", 2.0 * p.nkeys);
+    const int grid = listed ? l.max_units : (nr * p.S + 255) / 256 * 256;
     hipLaunchKernelGGL(k_c5_gather<C5_PPS>, dim3((unsigned)grid), dim3(C5_BLOCK), C5_GATHER_LDS, s->stream,
-                       stat ? nullptr : (const C3Unit *)units, (const int32_t *)nunits, part,
-                       in_place ? meta : (const uint32_t *)meta_t->p, ntiles, sd.nb, rstride, h_in, h_out,
-                       slice_stride, ovf, sdk, S, in_place && !direct ? (int64_t)nr : (int64_t)1);
+                       listed ? (const C3Unit *)units : nullptr, (const int32_t *)nunits, b.part,
+                       listed ? (const uint32_t *)meta_t->p : b.meta, p.ntiles, p.sides.nb, p.rstride, b.h_in,
+                       b.h_out, p.slice_stride, out.ovf, sdk, p.S, p.mstride);
     KERNEL_CHECK();
   }
-  if (sd.packed) {  // the hand-offs are applied by k_c5_dot_packed
-    *packed_ovf = ovf;
-    *keep = acc;
-  } else if (log_to_dot) {  // the dot kernel adds the hand-offs' terms
-    post->spill->log = ovf.log;
-    post->spill->n = ovf.n;
-    post->spill->cap = ovf.cap;
-    post->spill->hl = slice_stride;
-    post->spill->split = sd.pairs ? split : nullptr;  // per run: 1 = uint32 bins, 0 = packed pairs
-    post->spill->nb = sd.nb;
-    post->spill->tile_loops = direct ? post->tile_loops : nullptr;  // (direct: no transpose summed them)
-    post->spill->ntiles = direct ? post->ntiles : 0;
-  } else {
+  if (p.mode.log == C5Log::Overflow) {
     KernelTimer kt(s, "c3_overflow", 0.0);
-    hipLaunchKernelGGL(k_c3_overflow, dim3(16), dim3(256), 0, s->stream, ovf, h_in, h_out);
+    hipLaunchKernelGGL(k_c3_overflow, dim3(16), dim3(256), 0, s->stream, out.ovf, b.h_in, b.h_out);
     KERNEL_CHECK();
   }
+  return out;
 }
 
 // out[i] = Σ_s slices[s·stride + i] for both sides (n a multiple of 4).
@@ -1186,8 +1259,17 @@ __global__ __launch_bounds__(1024) void k_c5_dot_packed(const uint32_t *si, cons
   if (threadIdx.x == 0 && tot) atomicAdd(acc, tot);
 }
 
-// d_acc3 = [Σ in·out, self-loops, done]: the units kernel writes the self-loop
-// total and clears the other two (the caller needs no memset).
+// f(std::true_type / std::false_type) for a run-time flag: one call site per
+// template, every combination instantiated.
+template <class F>
+static void c5_with_flag(bool flag, F &&f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// d_acc3 = [Σ in·out, self-loops, done]: P1's tile-0 workgroup clears it, the
+// transpose (or, without one, the dot) adds the self-loops (the caller needs
+// no memset).
 template <int W, class SH>
 static void chain2_c5(Session *s, C5Cols<W> c, bool in_range, uint32_t *h_in, uint32_t *h_out,
                       unsigned long long *d_acc3, C2Spill *spill) {
@@ -1197,55 +1279,43 @@ static void chain2_c5(Session *s, C5Cols<W> c, bool in_range, uint32_t *h_in, ui
   BufPtr part = s->alloc(2 * c.rstride * c.ntiles);
   BufPtr meta = s->alloc(4 * nr * c.ntiles);
   BufPtr tl = s->alloc(4 * std::max<int64_t>(c.ntiles, 1));
-  C3Sides sd;
-  sd.split_x16 = c3_split_x16();
-  sd.nb = c.nb;
-  sd.t0[0] = sd.t0[1] = 0;
-  sd.t1[0] = sd.t1[1] = c.ntiles;
-  const int S = c5_slices(nr);
-  uint32_t ovf_cap = 0;
-  BufPtr post_acc = s->alloc(c5_post_acc_bytes(nr, S, sd.split_x16, 2 * c.n, nullptr, &ovf_cap));
-  // One slice (≥ 256 runs): no transpose and no work-list kernel — P1 writes
-  // run-major meta, every run is one exclusive P3 unit (hash-partitioned runs
-  // are near-uniform: no hub split at s24), the dot adds the self-loops.  s24
-  // (profiles/r05_ab_direct.txt): pipeline 1.000 → 0.980 ms, T 37 + U 8 µs
-  // gone, P1 +8 µs (scattered meta lines), P3 +13 µs (it now pays P1's dirty-line
-  // write-back that T used to).  CAPF_C5_DIRECT=0 keeps the transpose pipeline.
-  const char *de = getenv("CAPF_C5_DIRECT");
-  const bool direct_env = !(de && atoi(de) == 0);
-  const bool direct = direct_env && S == 1 && spill != nullptr;
+  const C5PostPlan plan = c5_plan_fused(c.nb, c.ntiles, c.rstride, 2 * c.n, spill != nullptr);
+  const bool direct = plan.mode.work == C5Work::Direct;
+  C5PostBufs bufs{(const uint16_t *)part->p,   (const uint32_t *)meta->p, h_in, h_out,
+                  s->alloc(plan.layout.bytes), (const uint32_t *)tl->p,   d_acc3};
   {
     KernelTimer kt(s, "c5_partition", (2.0 * W + 4.0) * c.n);
-    uint16_t *pp = (uint16_t *)part->p;
-    uint32_t *mp = (uint32_t *)meta->p;
-    uint32_t *tlp = (uint32_t *)tl->p, *zb = (uint32_t *)post_acc->p;
-    const int64_t zw = c5_post_zero_words(nr, ovf_cap, direct);
     const bool alias = c.u2 == c.u1 && c.v2 == c.v1;
-    const int rm = direct ? 1 : 0;
-    if (alias && !in_range) launch_c5<W, true, true, SH>(s, c, pp, mp, tlp, zb, zw, d_acc3, rm);
-    if (alias && in_range) launch_c5<W, true, false, SH>(s, c, pp, mp, tlp, zb, zw, d_acc3, rm);
-    if (!alias && !in_range) launch_c5<W, false, true, SH>(s, c, pp, mp, tlp, zb, zw, d_acc3, rm);
-    if (!alias && in_range) launch_c5<W, false, false, SH>(s, c, pp, mp, tlp, zb, zw, d_acc3, rm);
+    c5_with_flag(alias, [&](auto al) {
+      c5_with_flag(!in_range, [&](auto chk) {
+        launch_c5<W, decltype(al)::value, decltype(chk)::value, SH>(
+            s, c, (uint16_t *)part->p, (uint32_t *)meta->p, (uint32_t *)tl->p, (uint32_t *)bufs.acc->p,
+            plan.layout.zero_bytes / 4, d_acc3, direct ? 1 : 0);
+      });
+    });
   }
-  C3Post post{};
-  post.tile_loops = (const uint32_t *)tl->p;
-  post.ntiles = c.ntiles;
-  post.acc3 = d_acc3;
-  post.spill = spill;
-  const int64_t hl = (int64_t)c.nb * C2_BW;
-  sd.pairs = S == 1 && spill ? 1 : 0;  // packed-pair buckets (one uint32 per bin when split)
-  if (S == 1) {
-    c5_post(s, (const uint16_t *)part->p, (const uint32_t *)meta->p, sd, c.ntiles, c.rstride,
-            2 * c.n, 1, h_in, h_out, hl, false, nullptr, nullptr, &post, post_acc, direct);
-    return;
+  BufPtr sl;  // C, D with few runs: S slices per side, folded into the caller's histograms
+  if (plan.S > 1) {
+    sl = s->alloc(8 * plan.S * plan.slice_stride);
+    bufs.h_in = (uint32_t *)sl->p;
+    bufs.h_out = bufs.h_in + plan.S * plan.slice_stride;
   }
-  BufPtr sl = s->alloc(8 * S * hl);
-  uint32_t *si = (uint32_t *)sl->p, *so = si + S * hl;
-  c5_post(s, (const uint16_t *)part->p, (const uint32_t *)meta->p, sd, c.ntiles, c.rstride,
-          2 * c.n, S, si, so, hl, false, nullptr, nullptr, &post, post_acc);
-  hipLaunchKernelGGL(k_c5_fold, dim3(grid_for(hl / 4, 256, 1024)), dim3(256), 0, s->stream, si, so,
-                     S, hl, hl, h_in, h_out);
-  KERNEL_CHECK();
+  const C5PostOut out = c5_post(s, bufs, plan);
+  if (plan.mode.log == C5Log::Dot) {  // the dot kernel adds the hand-offs' terms
+    spill->log = out.ovf.log;
+    spill->n = out.ovf.n;
+    spill->cap = out.ovf.cap;
+    spill->hl = plan.slice_stride;
+    spill->split = plan.mode.counters == C5Counters::Pairs ? out.split : nullptr;
+    spill->nb = c.nb;
+    spill->tile_loops = direct ? bufs.tile_loops : nullptr;  // (direct: no transpose summed them)
+    spill->ntiles = direct ? c.ntiles : 0;
+  }
+  if (plan.S > 1) {
+    hipLaunchKernelGGL(k_c5_fold, dim3(grid_for(plan.slice_stride / 4, 256, 1024)), dim3(256), 0, s->stream,
+                       bufs.h_in, bufs.h_out, plan.S, plan.slice_stride, plan.slice_stride, h_in, h_out);
+    KERNEL_CHECK();
+  }
 }
 
 // ------------------------------------------------------------- sharded P1
@@ -1528,8 +1598,10 @@ __global__ __launch_bounds__(1024) void k_sharded_final(const unsigned long long
   if (threadIdx.x == 0) *out = (int64_t)(acc[0] + I * O - L);
 }
 
+// The sharded P1 for (W, wide mix, heavy-hitter hint: one more compare per key,
+// only ranks that hold a hub pay it).
 template <int TILE, bool TR>
-static auto c5s_kernel_t(int W, bool wide, bool hot) {
+static auto c5s_kernel(int W, bool wide, bool hot) {
   if (hot)
     return W == 3 ? (wide ? k_c5_shard_partition<3, true, TILE, true, TR> : k_c5_shard_partition<3, false, TILE, true, TR>)
            : W == 4 ? (wide ? k_c5_shard_partition<4, true, TILE, true, TR> : k_c5_shard_partition<4, false, TILE, true, TR>)
@@ -1539,15 +1611,19 @@ static auto c5s_kernel_t(int W, bool wide, bool hot) {
                   : (wide ? k_c5_shard_partition<8, true, TILE, false, TR> : k_c5_shard_partition<8, false, TILE, false, TR>);
 }
 
-template <int TILE>
-static auto c5s_kernel(int W, bool wide, bool hot) {
-  if (hot)  // a heavy-hitter hint: one more compare per key (only ranks that hold a hub pay it)
-    return W == 3 ? (wide ? k_c5_shard_partition<3, true, TILE, true> : k_c5_shard_partition<3, false, TILE, true>)
-           : W == 4 ? (wide ? k_c5_shard_partition<4, true, TILE, true> : k_c5_shard_partition<4, false, TILE, true>)
-                    : (wide ? k_c5_shard_partition<8, true, TILE, true> : k_c5_shard_partition<8, false, TILE, true>);
-  return W == 3 ? (wide ? k_c5_shard_partition<3, true, TILE, false> : k_c5_shard_partition<3, false, TILE, false>)
-         : W == 4 ? (wide ? k_c5_shard_partition<4, true, TILE, false> : k_c5_shard_partition<4, false, TILE, false>)
-                  : (wide ? k_c5_shard_partition<8, true, TILE, false> : k_c5_shard_partition<8, false, TILE, false>);
+// Bytes per id of P1's input columns — 8 (plain int64), 4 (FOR32) or 3
+// (FOR24) — or 0 when P1 cannot read them: all n must share one encoding, have
+// no validity mask and be 16-B aligned (vector loads); only a column without
+// rows may be null.
+static int c5_uniform_width(const ColView *cols, int n, const int64_t *rows) {
+  int nf = 0, n24 = 0;
+  for (int i = 0; i < n; ++i) {
+    if (cols[i].valid || (!cols[i].data && rows[i] > 0)) return 0;
+    if ((uintptr_t)cols[i].data & 15) return 0;
+    nf += cols[i].enc == ENC_FOR32;
+    n24 += cols[i].enc == ENC_FOR24;
+  }
+  return n24 == n ? 3 : nf == n ? 4 : nf + n24 == 0 ? 8 : 0;
 }
 
 // Buckets of 64 Ki mixed node indexes owned by `part` of `parts`.
@@ -1632,8 +1708,8 @@ uint8_t *node_owner_flags(Session *s, const ColView &key, int64_t n, int64_t lo,
 
 // Local 2-hop partial of `part`: Σ_{owned b} in[b]·out[b] − owned self-loops
 // into *d_partial (device, int64) — asynchronous on the session stream.
-// cols = {in-copy target, out-copy source, out-copy target}; all plain or all
-// FOR32, 16-B aligned, non-null.  Histograms live in session scratch.
+// cols = {in-copy target, out-copy source, out-copy target}, of one width
+// (c5_uniform_width).  Histograms live in session scratch.
 bool chain2_sharded(Session *s, const ColView *cols, int64_t n_in, int64_t n_out, int64_t lo,
                     int64_t n_nodes, int parts, int part, int64_t *d_partial, int64_t n_diag,
                     int nhot, const int64_t *hot_ids, bool trusted) {
@@ -1642,15 +1718,9 @@ bool chain2_sharded(Session *s, const ColView *cols, int64_t n_in, int64_t n_out
   owned_buckets(kbits, parts, part, &b0, &nbl);
   if (2 * nbl + 1 > C5S_MAXR) return false;
   if (n_in >= (int64_t(1) << 31) || n_out >= (int64_t(1) << 31)) return false;
-  int nf = 0, n24 = 0;
-  for (int i = 0; i < 3; ++i) {
-    if (cols[i].valid || (!cols[i].data && (i == 0 ? n_in : n_out) > 0)) return false;
-    if ((uintptr_t)cols[i].data & 15) return false;
-    nf += cols[i].enc == ENC_FOR32;
-    n24 += cols[i].enc == ENC_FOR24;
-  }
-  if (nf + n24 != 0 && nf != 3 && n24 != 3) return false;
-  const int W = n24 == 3 ? 3 : nf == 3 ? 4 : 8;
+  const int64_t rows[3] = {n_in, n_out, n_out};
+  const int W = c5_uniform_width(cols, 3, rows);
+  if (!W) return false;
   BufPtr acc = s->alloc(16);
   HIP_CHECK(hipMemsetAsync(acc->p, 0, 16, s->stream));
   unsigned long long *d_acc = (unsigned long long *)acc->p;  // [0] Σ in·out
@@ -1660,19 +1730,13 @@ bool chain2_sharded(Session *s, const ColView *cols, int64_t n_in, int64_t n_out
   // heavy hitters: distinct ids inside the node range (others could never match a key)
   uint32_t hot[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};  // mixed indexes (< 2^31: never all ones)
   int nh = 0;
-  {
-    const NodeMix mx = node_mix_for(kbits);
-    for (int i = 0; i < nhot && hot_ids && nh < C5S_MAXHOT; ++i) {
-      const int64_t x = hot_ids[i] - lo;
-      if (x < 0 || x >= n_nodes) continue;
-      const uint32_t ux = (uint32_t)x;
-      uint32_t hh = mx.wide ? ux * NODE_MIX_A : (uint32_t)((uint64_t)(ux & 0xFFFFFFu) * NODE_MIX_A);
-      hh &= mx.mask;
-      hh ^= hh >> mx.sh;
-      bool dup = false;
-      for (int j = 0; j < nh; ++j) dup |= hot[j] == hh;
-      if (!dup) hot[nh++] = hh;
-    }
+  for (int i = 0; i < nhot && hot_ids && nh < C5S_MAXHOT; ++i) {
+    const int64_t x = hot_ids[i] - lo;
+    if (x < 0 || x >= n_nodes) continue;
+    const uint32_t hh = node_mix((uint32_t)x, node_mix_for(kbits));
+    bool dup = false;
+    for (int j = 0; j < nh; ++j) dup |= hot[j] == hh;
+    if (!dup) hot[nh++] = hh;
   }
   if (nbl > 0) {
     C5Shard c;
@@ -1734,60 +1798,31 @@ bool chain2_sharded(Session *s, const ColView *cols, int64_t n_in, int64_t n_out
         KernelTimer kt(s, "c5_partition", (double)W * (n_in + 2 * n_out));
         // the trusted ring only where the ring runs (FOR24 / FOR32 columns)
         const bool tr = trusted && W != 8 && c.upf;
-        auto kern = tile == C5S_TILE ? (tr ? c5s_kernel_t<C5S_TILE, true>(W, kbits > 24, nh > 0)
-                                           : c5s_kernel<C5S_TILE>(W, kbits > 24, nh > 0))
-                                     : (tr ? c5s_kernel_t<16384, true>(W, kbits > 24, nh > 0)
-                                           : c5s_kernel<16384>(W, kbits > 24, nh > 0));
+        auto kern = tile == C5S_TILE ? (tr ? c5s_kernel<C5S_TILE, true>(W, kbits > 24, nh > 0)
+                                           : c5s_kernel<C5S_TILE, false>(W, kbits > 24, nh > 0))
+                                     : (tr ? c5s_kernel<16384, true>(W, kbits > 24, nh > 0)
+                                           : c5s_kernel<16384, false>(W, kbits > 24, nh > 0));
         hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(C5_BLOCK), 0, s->stream, c,
                            (uint16_t *)partb->p, (uint32_t *)meta->p, tile_acc, rstride);
         KERNEL_CHECK();
       }
-      {
-        C3Sides sd;
-        sd.split_x16 = c3_split_x16();
-        sd.nb = nbl;
-        sd.t0[0] = 0;
-        sd.t1[0] = c.t_in;
-        sd.t0[1] = c.t_in;
-        sd.t1[1] = ntiles;
-        const int S = c5_slices(nr);
-        const int64_t hl = (int64_t)nbl * C2_BW;
-        {
-        // packed when several slices per run (G ≥ 4 at s24): with one slice the runs
-        // are whole buckets whose hub bins log many hand-offs (measured G = 2:
-        // packed dot 41 µs vs uint32 dot + overflow 22 µs)
-        sd.packed = S >= 2;
-        if (sd.packed) {
-          // packed uint16 slices: half the slice bytes written by P3 and read by the dot
-          const int64_t hw = (int64_t)nbl * C2_WORDS;
-          BufPtr sl = s->alloc(8 * S * hw);
-          uint32_t *si = (uint32_t *)sl->p, *so = si + S * hw;
-          C3Ovf ovf{};
-          BufPtr keep;
-          c5_post(s, (const uint16_t *)partb->p, (const uint32_t *)meta->p, sd, ntiles, rstride,
-                  n_in + n_out, S, si, so, hw, true, &ovf, &keep);
-          KernelTimer kt(s, "chain2_dot", 8.0 * S * hw);
-          hipLaunchKernelGGL(k_c5_dot_packed, dim3(grid_for(hw / 4, 1024, dot_grid(s->num_cus))), dim3(1024),
-                             0, s->stream, si, so, S, hw, hw, ovf, d_acc);
-          KERNEL_CHECK();
-        } else {
-        BufPtr sl = s->alloc(8 * S * hl);
-        uint32_t *si = (uint32_t *)sl->p, *so = si + S * hl;
-        // static work list (no units kernel): S tile ranges per run; a rank's
-        // runs hold ≤ 1.4 × the mean at s24 (no hub splits happen)
-        c5_post(s, (const uint16_t *)partb->p, (const uint32_t *)meta->p, sd, ntiles, rstride,
-                n_in + n_out, S, si, so, hl, true);
-        KernelTimer kt(s, "chain2_dot", 8.0 * S * hl);
-        // one block per CU: every block ends in one same-address device atomic
-        // (G = 8 rank: 256 blocks 18.5 µs, 1024 24.4 µs, 2048 36 µs)
-        // one block per CU (each block ends in one device atomic); 16 waves per
-        // block keep 8·S·… loads in flight per CU (256 threads: latency bound)
-        hipLaunchKernelGGL(k_c5_dot_slices, dim3(grid_for(hl / 4, 1024, dot_grid(s->num_cus))),
-                           dim3(1024), 0, s->stream, si, so, S, hl, hl, d_acc);
-        KERNEL_CHECK();
-        }
-        }
-      }
+      const C5PostPlan plan = c5_plan_sharded(nbl, c.t_in, ntiles, rstride, n_in + n_out);
+      const int S = plan.S;
+      const int64_t hl = plan.slice_stride;  // words per slice and side
+      BufPtr sl = s->alloc(8 * S * hl);
+      uint32_t *si = (uint32_t *)sl->p, *so = si + S * hl;
+      const C5PostOut post = c5_post(s, C5PostBufs{(const uint16_t *)partb->p, (const uint32_t *)meta->p, si, so,
+                                                   s->alloc(plan.layout.bytes), nullptr, nullptr}, plan);
+      KernelTimer kt(s, "chain2_dot", 8.0 * S * hl);
+      // one block per CU: every block ends in one same-address device atomic
+      // (G = 8 rank: 256 blocks 18.5 µs, 1024 24.4 µs, 2048 36 µs); 16 waves per
+      // block keep 8·S·… loads in flight per CU (256 threads: latency bound)
+      const dim3 grid(grid_for(hl / 4, 1024, dot_grid(s->num_cus)));
+      if (plan.mode.log == C5Log::PackedDot)  // F: the dot applies the hand-off log
+        hipLaunchKernelGGL(k_c5_dot_packed, grid, dim3(1024), 0, s->stream, si, so, S, hl, hl, post.ovf, d_acc);
+      else  // E: k_c3_overflow already did
+        hipLaunchKernelGGL(k_c5_dot_slices, grid, dim3(1024), 0, s->stream, si, so, S, hl, hl, d_acc);
+      KERNEL_CHECK();
     }
   }
   hipLaunchKernelGGL(k_sharded_final, dim3(1), dim3(1024), 0, s->stream, (const unsigned long long *)d_acc,
@@ -1804,8 +1839,8 @@ int chain2_hist_bits(int64_t len) {
 
 int64_t chain2_hist_len(int64_t len) { return int64_t(1) << chain2_hist_bits(len); }
 
-// cols = {start(r1), end(r1), start(r2), end(r2)}: non-null INTEGER columns,
-// all plain or all FOR32.  h_in / h_out hold chain2_hist_len(hi − lo + 1)
+// cols = {start(r1), end(r1), start(r2), end(r2)}: non-null INTEGER columns
+// of one width (c5_uniform_width).  h_in / h_out hold chain2_hist_len(hi − lo + 1)
 // counters each, indexed by node_mix(id − lo); every counter is written (no
 // memset needed).  in_range: every id of the four columns lies in [lo, hi]
 // (column statistics), so P1 skips the range tests.  The self-loop count is
@@ -1821,62 +1856,23 @@ bool chain2_partitioned(Session *s, const ColView *cols, int64_t n, int64_t lo, 
   const int64_t nb = (int64_t(1) << kbits) / C2_BW;
   if (2 * nb + 1 > C5Big::MAXR) return false;  // + the dummy run
   if (n >= (int64_t(1) << 30)) return false;   // 2·n keys: 32-bit element indices in `part`
-  int nf = 0, n24 = 0;
-  for (int i = 0; i < 4; ++i) {
-    if (cols[i].valid || !cols[i].data) return false;
-    if ((uintptr_t)cols[i].data & 15) return false;  // 16-B vector loads
-    nf += cols[i].enc == ENC_FOR32;
-    n24 += cols[i].enc == ENC_FOR24;
-  }
-  if (n24 != 0 && n24 != 4) return false;
-  if (n24 == 0 && nf != 0 && nf != 4) return false;
-  auto fill = [&](auto &c) {
-    c.u1 = cols[0].data;
-    c.v1 = cols[1].data;
-    c.u2 = cols[2].data;
-    c.v2 = cols[3].data;
-    const bool f = nf == 4 || n24 == 4;
-    c.bu1 = f ? cols[0].base : 0;
-    c.bv1 = f ? cols[1].base : 0;
-    c.bu2 = f ? cols[2].base : 0;
-    c.bv2 = f ? cols[3].base : 0;
-    c.n = n;
-    c.lo = lo;
-    c.len = (uint64_t)len;
-    c.nb = (int)nb;
-    c.mix = node_mix_for(kbits);
-  };
+  const int64_t rows[4] = {n, n, n, n};
+  const int width = c5_uniform_width(cols, 4, rows);
+  if (!width) return false;
   const bool small = 2 * nb + 1 <= C5Small::MAXR;
-  if (n24 == 4) {
-    C5Cols<3> c;
-    fill(c);
-    if (small)
-      chain2_c5<3, C5Small>(s, c, in_range, h_in, h_out, d_acc3, spill);
-    else
-      chain2_c5<3, C5Big>(s, c, in_range, h_in, h_out, d_acc3, spill);
-    return true;
-  }
-  if (nf == 4) {
-    C5Cols<4> c;
-    fill(c);
-    if (small)
-      chain2_c5<4, C5Small>(s, c, in_range, h_in, h_out, d_acc3, spill);
-    else
-      chain2_c5<4, C5Big>(s, c, in_range, h_in, h_out, d_acc3, spill);
-    return true;
-  }
-  C5Cols<8> c;
-  fill(c);
-  if (small)
-    chain2_c5<8, C5Small>(s, c, in_range, h_in, h_out, d_acc3, spill);
-  else
-    chain2_c5<8, C5Big>(s, c, in_range, h_in, h_out, d_acc3, spill);
+  auto run = [&](auto w, auto shape) {
+    constexpr int W = decltype(w)::value;
+    auto base = [&](int i) { return W != 8 ? cols[i].base : int64_t(0); };
+    const C5Cols<W> c{cols[0].data, cols[1].data, cols[2].data, cols[3].data, base(0), base(1), base(2), base(3),
+                      n, lo, (uint64_t)len, (int)nb, /* ntiles, rstride: chain2_c5 */ 0, 0, node_mix_for(kbits)};
+    chain2_c5<W, decltype(shape)>(s, c, in_range, h_in, h_out, d_acc3, spill);
+  };
+  auto shaped = [&](auto w) { small ? run(w, C5Small{}) : run(w, C5Big{}); };
+  if (width == 3) shaped(std::integral_constant<int, 3>{});
+  else if (width == 4) shaped(std::integral_constant<int, 4>{});
+  else shaped(std::integral_constant<int, 8>{});
   return true;
 }
-
-}  // namespace capf
-
-namespace capf {
 
 // ------------------------------------------ partitioned semi-join count
 // Σ_rows bit[key − lo]: the root message of the 1-hop label count

@@ -42,12 +42,16 @@ struct NodeMix {
 constexpr uint32_t NODE_MIX_A = 0xB5297Bu;  // odd, < 2^24
 
 template <bool WIDE>
-__device__ inline uint32_t node_mix_t(uint32_t x, NodeMix m) {
+__host__ __device__ inline uint32_t node_mix_t(uint32_t x, NodeMix m) {
+#ifdef __HIP_DEVICE_COMPILE__
   const uint32_t h = (WIDE ? x * NODE_MIX_A : __umul24(x, NODE_MIX_A)) & m.mask;
+#else  // the host's __umul24: low 32 bits of the 24-bit product
+  const uint32_t h = (WIDE ? x * NODE_MIX_A : (x & 0xFFFFFFu) * NODE_MIX_A) & m.mask;
+#endif
   return h ^ (h >> m.sh);
 }
 
-__device__ inline uint32_t node_mix(uint32_t x, NodeMix m) {
+__host__ __device__ inline uint32_t node_mix(uint32_t x, NodeMix m) {
   return m.wide ? node_mix_t<true>(x, m) : node_mix_t<false>(x, m);
 }
 

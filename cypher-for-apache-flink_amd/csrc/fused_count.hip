@@ -1340,6 +1340,13 @@ static bool host_trace() {
 }
 static double g_trace_t0 = 0;
 
+// CAPF_CHAIN2 = "atomic" | "partitioned": which histograms the 2-hop count of
+// n rels builds (default: partitioned from 2^22 rels)
+static bool chain2_want_partitioned(int64_t n) {
+  const char *mode = getenv("CAPF_CHAIN2");
+  return mode ? strcmp(mode, "partitioned") == 0 : n >= (int64_t(1) << 22);
+}
+
 // acc = (Σ in·out, self-loop term) → the count, on the device
 __global__ void k_partial_minus_loops(const unsigned long long *acc, int64_t *out) {
   if (threadIdx.x == 0) *out = (int64_t)(acc[0] - acc[1]);
@@ -1397,10 +1404,8 @@ static bool run_chain2(Session *s, const JoinGraph &g, const Chain2 &c, uint64_t
     a.loops = (unsigned long long *)acc->p + 1;
     a.mixed = 0;
     a.mix = node_mix_for(0);
-    const char *mode = getenv("CAPF_CHAIN2");  // "atomic" | "partitioned" (default: by size)
     const bool want_part = all_ones && wa.map.m.lo == lo && wc.map.m.lo == lo &&
-                           wa.map.m.hi == hi && wc.map.m.hi == hi &&
-                           (mode ? strcmp(mode, "partitioned") == 0 : n >= (int64_t(1) << 22));
+                           wa.map.m.hi == hi && wc.map.m.hi == hi && chain2_want_partitioned(n);
     bool in_range = true;  // column statistics (cached): all endpoint ids inside [lo, hi]
     for (int col : {c.u1, c.v1, c.u2, c.v2}) {
       const ColStats &st = column_stats(s, R.cols[col]);
@@ -2039,8 +2044,7 @@ extern "C" capf_status capf_chain2_local_hists(capf_session *cs, capf_table *rel
     a.loops = (unsigned long long *)acc->p + 1;
     a.mixed = 1;
     a.mix = node_mix_for(chain2_hist_bits(n_nodes));
-    const char *mode = getenv("CAPF_CHAIN2");
-    const bool want_part = mode ? strcmp(mode, "partitioned") == 0 : a.n >= (int64_t(1) << 22);
+    const bool want_part = chain2_want_partitioned(a.n);
     const ColView pc[4] = {a.u1, a.v1, a.u2, a.v2};
     const ColStats &ss = column_stats(s, src), &sd = column_stats(s, dst);
     const bool in_range = ss.min >= a.lo && ss.max <= a.hi && sd.min >= a.lo && sd.max <= a.hi;

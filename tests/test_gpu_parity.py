@@ -101,6 +101,42 @@ def test_two_hop_partition_variants(gpu_session, monkeypatch, variant, compact, 
     assert got == cmodel.count_2hop(src, dst, nodes or 1 << scale)
 
 
+@pytest.fixture(scope="module")
+def _sparse_two_hop_expect():
+    """Closed-form counts of the 300001-rel prefixes below, computed once per (scale, nodes)."""
+    memo = {}
+
+    def expect(scale, nodes):
+        if (scale, nodes) not in memo:
+            src, dst = cmodel.rmat(scale, count=300001)
+            memo[scale, nodes] = cmodel.count_2hop(src, dst, nodes or 1 << scale)
+        return memo[scale, nodes]
+    return expect
+
+
+@pytest.mark.parametrize("direct", ["1", "0"], ids=["direct", "transpose"])
+@pytest.mark.parametrize("compact", [False, True, 3], ids=["int64", "for32", "for24"])
+@pytest.mark.parametrize("scale,nodes", [(23, None), (23, 5_000_001), (25, None), (25, 20_000_003)])
+def test_two_hop_one_slice_pipelines(gpu_session, monkeypatch, _sparse_two_hop_expect, direct, compact,
+                                     scale, nodes):
+    """The one-slice (≥ 256 runs) pipelines of the partitioned count at a small
+    rel count: the default without a transpose or a work list (P1 writes
+    run-major meta, one exclusive unit per run) and CAPF_C5_DIRECT=0 (transpose
+    + device work list).  Scale 23: 256 runs, the small P1 shape; scale 25: the
+    big P1 shape with the 32-bit mix.  The clipped node tables take the
+    range-checked P1 and the dummy run (~60 k rels have an endpoint outside).
+    Closed form (4 self-loops each): s23 2,636,731; s23 / 5,000,001 nodes
+    2,047,547; s25 1,052,300; s25 / 20,000,003 nodes 817,358."""
+    monkeypatch.setenv("CAPF_CHAIN2", "partitioned")
+    monkeypatch.setenv("CAPF_C5_DIRECT", direct)
+    g = rmat_graph(gpu_session, scale, compact=compact, count=300001, n_nodes=nodes)
+    expect = _sparse_two_hop_expect(scale, nodes)
+    for _ in range(2):  # the second query reuses the session's scratch as the first left it
+        got = run(g, TWO_HOP)[0]["count"]
+        assert gpu_session.last_plan() == "fused_chain2"
+        assert got == expect
+
+
 @pytest.mark.parametrize("query", ["two_hop", "triangle", "one_hop_person", "grouped"])
 def test_count_async_matches_size(gpu_session, query):
     """capf_table_count_async: a queue of in-flight counts (no host wait per
@@ -775,23 +811,28 @@ def test_local_hists_hashed_layout(gpu_session, monkeypatch, variant, compact, s
     assert loops == int((s == d).sum())
 
 
-@pytest.mark.parametrize("n", [1 << 17, 100000], ids=["in_range", "checked"])
+@pytest.mark.parametrize("bits,n", [(17, 1 << 17), (17, 100000), (23, 1 << 23), (23, 5_000_001)],
+                         ids=["in_range", "checked", "direct_in_range", "direct_checked"])
 @pytest.mark.parametrize("compact", [False, True, 3], ids=["int64", "for32", "for24"])
-def test_two_hop_hub_overflow(gpu_session, monkeypatch, n, compact):
+def test_two_hop_hub_overflow(gpu_session, monkeypatch, bits, n, compact):
     """Hubs with in/out degree far above 2^16 in one P3 unit: the packed
     uint16 LDS counters hand off 2^15 per overflow (k_c3_overflow) and the
-    hub runs are split into atomically flushed units; the count stays exact."""
+    hub runs are split into atomically flushed units; the count stays exact.
+    Ids over [0, 2^23) make 256 runs: the default one-slice pipeline, where a
+    hub's pair counter hands off inside an exclusive unit and the dot kernel
+    folds the log in."""
     from capf_amd.graph import ElementTable, ScanGraph as SG
     from capf_amd.expr import T_INT
     monkeypatch.setenv("CAPF_CHAIN2", "partitioned")
     rng = np.random.default_rng(11)
     m = 1 << 20
-    src = rng.integers(0, 1 << 17, m)  # ids ≥ n (checked case) fall outside the node table
-    dst = rng.integers(0, 1 << 17, m)
+    src = rng.integers(0, 1 << bits, m)  # ids ≥ n (checked cases) fall outside the node table
+    dst = rng.integers(0, 1 << bits, m)
+    hub2 = 70000 if bits == 17 else 4_500_000  # (above 2^22, inside both node tables)
     src[: 300000] = 5            # out-hub
     dst[100000: 400000] = 9      # in-hub
-    dst[500000: 600000] = 70000  # second in-hub in another bucket
-    src[590000: 700000] = 70000
+    dst[500000: 600000] = hub2   # second in-hub in another bucket
+    src[590000: 700000] = hub2
     dst[650000: 660000] = src[650000: 660000]  # self-loops
     rels = gpu_session.table([("id", T_INT, np.arange(m), None), ("source", T_INT, src, None),
                               ("target", T_INT, dst, None)])
