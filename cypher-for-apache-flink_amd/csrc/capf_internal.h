@@ -650,6 +650,10 @@ struct C2Spill {
   // (the pipeline without a transpose kernel)
   const uint32_t *tile_loops = nullptr;
   int64_t ntiles = 0;
+  // the pipeline already wrote *fin (P3's probe mode: in-side counters probed
+  // with the out keys, no histograms stored): no dot kernel; log / n then hold
+  // only the entries that overflowed a unit's LDS hot table (diagnostics)
+  bool fin_written = false;
 };
 // d_acc3 = [Σ in·out, self-loops, done counter] (device): the pipeline writes
 // the self-loop total into [1] and clears [0] and [2] itself (no memset needed)

@@ -28,8 +28,19 @@
 //         plain stores (no memset anywhere); a counter reaching 2^15 hands
 //         that much off to a log (rare)
 //   D  k_chain2_dot_pairs  Σ in·out + the log's terms + self-loops (fused_count.hip)
-// That is the default at ≥ 256 runs (s24).  The other modes of the fused count
-// (C5PostPlan; the table of all six is in DESIGN.md) add
+// That is mode A, the default at 256 runs (128 buckets).  From 256 buckets on
+// (s24) the default is mode P, which has no out histogram, no flush and no D:
+//   P3 k_c5_gather<.., PROBE>  unit b is bucket b.  Σ_b in[b]·out[b] = Σ_{r2}
+//         in[start(r2)], so the unit counts in-run b into LDS as above, then
+//         streams out-run nb + b through the same walker and sums one 16-bit
+//         LDS read of in[key] per out key (identical addresses broadcast: no
+//         atomics, no conflicts).  A counter reaching 2^15 hands off to a
+//         per-unit LDS hot table (the global log only when that is full);
+//         before the probe every half becomes in mod 2^16 and the few keys of
+//         in-degree ≥ 2^16 have their probes counted per wave.  Each unit adds
+//         its Σ and its share of the self-loops; the last one writes the count.
+// The other modes of the fused count
+// (C5PostPlan; the table of all seven is in DESIGN.md) add
 //   T  k_c3_transpose  [tile][run] → [run][tile] meta, per-run totals, Σ self-loops
 //   U  k_c3_units      device work list (one unit per run; hub-heavy runs split)
 //   O  k_c3_overflow   adds the logged hand-offs to the histograms
@@ -596,6 +607,67 @@ __device__ inline void c3_handoff(uint32_t *w, uint32_t inc, uint32_t hidx, uint
   if (k < o.cap) o.log[k] = make_uint2(hidx, side | (1u << 16));
 }
 
+// Mode P (probe): the in counters never leave LDS.  A half that reaches 2^15
+// hands that much off to the unit's LDS hot table (open addressing, the key
+// claimed by atomicCAS, a uint32 total per slot); when the table is full, to
+// the global log as (bucket·2^16 + key, count) — exact, slow.  After the in-run
+// every half holds in[key] mod 2^16 (0xFFFF: the key's counts are in the
+// global log), what a hot key has beyond 16 bits sits in the unit's list of
+// special keys, and the out keys read the halves instead of counting.
+constexpr int C5_HOT = 512;  // hot-table slots
+constexpr uint32_t C5_HOT_EMPTY = 0xFFFFFFFFu;
+
+struct C5Probe {
+  unsigned long long *acc3;    // [Σ in·out, self-loops, done]
+  int64_t *fin;                // the count: the pinned host scalar or the async slot
+  const uint32_t *tile_loops;  // P1's per-tile self-loop counts
+  uint32_t hotcap;             // hot-table slots in use (1..C5_HOT; CAPF_C5_HOTCAP: tests)
+};
+
+__device__ inline void c5_log_append(uint2 *log, uint32_t *n, uint32_t cap, uint32_t gkey, uint32_t count) {
+  const uint32_t k = atomicAdd(n, 1u);
+  if (k < cap)
+    __hip_atomic_store((unsigned long long *)&log[k], (unsigned long long)gkey | (unsigned long long)count << 32,
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ inline uint2 c5_log_entry(const uint2 *log, uint32_t i) {
+  const unsigned long long e =
+      __hip_atomic_load((const unsigned long long *)&log[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return make_uint2((uint32_t)e, (uint32_t)(e >> 32));
+}
+
+// Slow path of an overflowing add in mode P (one copy per step functor: see
+// the counting loop).
+__device__ inline void c5_hot_handoff(uint32_t *w, uint32_t inc, uint32_t *hk, uint32_t *hv,
+                                                         uint32_t hotcap, uint32_t key, uint32_t gkey, uint2 *log,
+                                                         uint32_t *logn, uint32_t logcap) {
+  atomicSub(w, inc << 15);
+  uint32_t s = ((key * 0x9E3779B1u) >> 16) % hotcap;
+  for (uint32_t k = 0; k < hotcap; ++k) {
+    const uint32_t prev = atomicCAS(&hk[s], C5_HOT_EMPTY, key);
+    if (prev == C5_HOT_EMPTY || prev == key) {
+      atomicAdd(&hv[s], 0x8000u);
+      return;
+    }
+    s = s + 1 == hotcap ? 0u : s + 1;
+  }
+  c5_log_append(log, logn, logcap, gkey, 0x8000u);  // table full
+}
+
+// Σ of the global log's counts for gkey (a unit's own entries: all written
+// before the barrier that ends its in-run; zero entries add nothing).
+__device__ inline uint32_t c5_log_sum(const uint2 *log, const uint32_t *logn, uint32_t logcap,
+                                                         uint32_t gkey) {
+  const uint32_t n = min(__hip_atomic_load(logn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), logcap);
+  uint32_t t = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint2 e = c5_log_entry(log, i);
+    t += e.x == gkey ? e.y : 0u;
+  }
+  return t;
+}
+
 // P3 pieces per lane per step, double-buffered (s24: 2 → 0.49 ms; 4 spills → 0.66 ms)
 constexpr int C5_PPS = 2;
 
@@ -606,6 +678,10 @@ struct C5WaveTab {
 
 constexpr size_t C5_GATHER_LDS =
     4 * (C2_WORDS + C5_CORR) + 2 * sizeof(C5WaveTab) * (C5_BLOCK / WAVE);
+// mode P: + the out side's correction bins, the hot table (keys, totals), the specials
+// (keys, extras), the block reduction, the specials' count and the hot pad bins' mask
+constexpr size_t C5_PROBE_LDS = C5_GATHER_LDS + 4 * C5_CORR + 16 * C5_HOT + 8 * 17 + 16;
+static_assert(C5_GATHER_LDS % 8 == 0 && C5_PROBE_LDS <= 160 * 1024, "P3 LDS layout");
 
 __device__ inline int64_t uniform64(int64_t v) {
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
@@ -638,7 +714,16 @@ __device__ inline int64_t uniform64(int64_t v) {
 // moderately hot keys); so were a per-wave hot-key register, rotating and
 // fully deduplicating each piece's 8 keys, and a third piece buffer depth vs two
 // (no gain at s24).
-template <int PPS>
+//
+// PROBE (mode P, the fused 2-hop count at ≥ 256 buckets): unit b is bucket b.
+// Σ_b in[b]·out[b] = Σ_{r2} in[start(r2)], so out[] is never built: the unit
+// counts in-run b as above (phase 1, hand-offs to the LDS hot table), then the
+// same walker streams out-run nb + b and every out key is one 16-bit LDS read
+// of its in counter, summed in registers (phase 2: same-address reads
+// broadcast — no atomics, no merge, no overflow tracking).  Pad and dead-lane
+// keys are probed like real ones and Σ_{i<64} corr_out[i]·in[i] is subtracted.
+// No counter leaves LDS; the last unit to finish writes the count (no dot).
+template <int PPS, bool PROBE = false>
 __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
                                                             const int32_t *nunits,
                                                             const uint16_t *part,
@@ -646,10 +731,10 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
                                                             int nb, int64_t rstride, uint32_t *h_in,
                                                             uint32_t *h_out, int64_t slice_stride,
                                                             C3Ovf ovf,
-                                                            C3Sides sd, int S, int64_t mstride) {
+                                                            C3Sides sd, int S, int64_t mstride, C5Probe pr) {
   // units == null: the static work list of a node-partitioned rank — unit
   // (run, k) counts tile range k of S of the run's side into slice k
-  const int nu = units ? *nunits : 2 * sd.nb * S;
+  const int nu = PROBE ? sd.nb : units ? *nunits : 2 * sd.nb * S;
   const int ui = c3_unit_of((int)blockIdx.x);
   if (ui >= nu) return;
   extern __shared__ __attribute__((aligned(16))) uint32_t words[];
@@ -657,8 +742,19 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
   constexpr uint32_t STEP = WAVE * PPS;
   uint32_t *corr = words + C2_WORDS;
   C5WaveTab *tabs = (C5WaveTab *)(corr + C5_CORR);  // 2 per wave
+  // mode P only (C5_PROBE_LDS)
+  uint32_t *corr_out = (uint32_t *)(tabs + 2 * NW);
+  uint32_t *hk = corr_out + C5_CORR, *hv = hk + C5_HOT, *sk = hv + C5_HOT, *sx = sk + C5_HOT;
+  unsigned long long *red = (unsigned long long *)(sx + C5_HOT);
+  uint32_t *nspec = (uint32_t *)(red + 17), *hotpad = nspec + 1;  // [1], [2]
   C3Unit u;
-  if (units) {
+  if constexpr (PROBE) {  // unit b: in-run b, then out-run nb + b, every tile
+    u.run = ui;
+    u.exclusive = 1;
+    u.t0 = sd.t0[0];
+    u.t1 = sd.t1[0];
+    u.slice = 0;
+  } else if (units) {
     u = units[ui];
   } else {
     const int k = ui % S, sdi = ui / S >= sd.nb ? 1 : 0;
@@ -674,12 +770,20 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
   const uint32_t log_base = (uint32_t)((int64_t)(u.run % nb) * C2_BW);  // packed: side bin of key 0
   const uint32_t hist_base = (uint32_t)(u.slice * slice_stride + (int64_t)(u.run % nb) * C2_BW);
   for (int i = threadIdx.x; i < C2_WORDS + C5_CORR; i += C5_BLOCK) words[i] = 0;
+  if constexpr (PROBE) {
+    for (int i = threadIdx.x; i < C5_HOT; i += C5_BLOCK) {
+      hk[i] = C5_HOT_EMPTY;
+      hv[i] = 0;
+    }
+    if (threadIdx.x < C5_CORR) corr_out[threadIdx.x] = 0;
+    if (threadIdx.x < 3) nspec[threadIdx.x] = 0;  // + hotpad[0..1]
+  }
   // A split run's units flush with atomic adds into bins that must start at
   // zero: the first unit of (run, slice) to start sets its claim bit and clears
   // the bucket in HBM, then its ready bit; the others wait for the ready bit
   // before flushing.  A waiter only ever waits on a workgroup already running
   // (the claimer), so the wait ends — no clearing kernel, no kernel boundary.
-  const bool zsplit = sd.claim && !u.exclusive;
+  const bool zsplit = !PROBE && sd.claim && !u.exclusive;
   if (zsplit) {
     __shared__ int zown;
     if (threadIdx.x == 0) zown = !(atomicOr(&sd.claim[u.run], 2 << u.slice) & (2 << u.slice));
@@ -699,6 +803,7 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
   const uint4 *part4 = (const uint4 *)part;
   // run-major meta_t (mstride 1) or P1's tile-major meta read in place (mstride nr)
   const uint32_t *m = meta_t + (mstride == 1 ? (int64_t)u.run * ntiles : (int64_t)u.run);
+  (void)corr_out, (void)hk, (void)hv, (void)sk, (void)sx, (void)red, (void)nspec, (void)hotpad;
   const int64_t ut = u.t1 - u.t0;
   const int64_t w0 = uniform64(u.t0 + ut * wave / NW), w1 = uniform64(u.t0 + ut * (wave + 1) / NW);
   const uint32_t rs8 = (uint32_t)(rstride / 8);
@@ -795,6 +900,7 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
     if (acc & 0x80008000u) {
       // rare: some half reached 2^15 — find the add(s) that crossed it (the
       // half before the add was < 2^15 and the add took it to ≥ 2^15)
+      uint32_t xm = 0;  // mode P: the crossing adds, bit 8·j + e
 #pragma unroll
       for (int j = 0; j < PPS; ++j) {
         const bool live = p0 + j * WAVE + lane < total;
@@ -807,92 +913,301 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
           if (e > 0 && dup[j][e]) continue;
           const uint32_t sh = (key >> 15) << 4;
           const uint32_t oh = (old[j][e] >> sh) & 0xFFFFu;
-          if (oh < 0x8000u && oh + inc >= 0x8000u)
-            c3_handoff(&words[key & (C2_WORDS - 1)], 1u << sh, (sd.packed ? log_base : hist_base) + key,
-                       side, ovf);
+          if (oh < 0x8000u && oh + inc >= 0x8000u) {
+            if constexpr (PROBE)
+              xm |= 1u << (8 * j + e);
+            else
+              c3_handoff(&words[key & (C2_WORDS - 1)], 1u << sh, (sd.packed ? log_base : hist_base) + key, side,
+                         ovf);
+          }
+        }
+      }
+      if constexpr (PROBE) {
+        // ONE copy of the hand-off per step functor, in a loop over the
+        // crossing adds: a copy (or a call) per add costs the counting loop
+        // registers — scratch
+        while (xm) {
+          const uint32_t idx = (uint32_t)__builtin_ctz(xm);
+          xm &= xm - 1;
+          uint32_t kw = 0;
+#pragma unroll
+          for (int j = 0; j < PPS; ++j) {
+            const bool live = p0 + j * WAVE + lane < total;
+            const uint32_t wd[4] = {live ? v[j].x : dead_keys.x, live ? v[j].y : dead_keys.y,
+                                    live ? v[j].z : dead_keys.z, live ? v[j].w : dead_keys.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) kw = (idx >> 1) == (uint32_t)(4 * j + q) ? wd[q] : kw;
+          }
+          const uint32_t key = (idx & 1) ? kw >> 16 : kw & 0xFFFF;
+          c5_hot_handoff(&words[key & (C2_WORDS - 1)], 1u << ((key >> 15) << 4), hk, hv, pr.hotcap, key,
+                         log_base + key, ovf.log, ovf.n, ovf.cap);
         }
       }
     }
   };
-  if (w0 < w1) {
-    int64_t tb = uniform64(w0);
-    int buf = 0;
-    uint32_t total = setup(tb, buf), p0 = 0;
-    while (total == 0) {  // first non-empty batch
-      tb += WAVE;
-      if (tb >= w1) break;
-      buf ^= 1;
-      total = setup(tb, buf);
-    }
-    if (total) {
-      // the next step: the same batch, or the next non-empty one
-      // scalar (wave-uniform) loop state: readfirstlane keeps it in SGPRs
-      auto advance = [&]() -> bool {
-        if (p0 + STEP < total) {
-          p0 = (uint32_t)__builtin_amdgcn_readfirstlane(p0 + STEP);
+  // The wave's stream walker: every step of run `m` (setup / fetch / advance,
+  // three rotating piece buffers) handed to `step`.
+  auto walk = [&](auto step) __attribute__((always_inline)) {
+    if (w0 < w1) {
+      int64_t tb = uniform64(w0);
+      int buf = 0;
+      uint32_t total = setup(tb, buf), p0 = 0;
+      while (total == 0) {  // first non-empty batch
+        tb += WAVE;
+        if (tb >= w1) break;
+        buf ^= 1;
+        total = setup(tb, buf);
+      }
+      if (total) {
+        // the next step: the same batch, or the next non-empty one
+        // scalar (wave-uniform) loop state: readfirstlane keeps it in SGPRs
+        auto advance = [&]() -> bool {
+          if (p0 + STEP < total) {
+            p0 = (uint32_t)__builtin_amdgcn_readfirstlane(p0 + STEP);
+            return true;
+          }
+          do {
+            tb = uniform64(tb + WAVE);
+            if (tb >= w1) return false;
+            buf ^= 1;
+            total = setup(tb, buf);
+            p0 = 0;
+          } while (total == 0);
           return true;
-        }
-        do {
-          tb = uniform64(tb + WAVE);
-          if (tb >= w1) return false;
-          buf ^= 1;
-          total = setup(tb, buf);
-          p0 = 0;
-        } while (total == 0);
-        return true;
-      };
-      {
-        // three rotating piece buffers: the loads of steps i+1 and i+2 are in
-        // flight while step i counts (unrolled by 3, no register copies)
-        uint4 va[PPS], vb[PPS], vc[PPS];
-        uint32_t pa, ta, pb, tb2, pc, tc;
-        pa = p0;
-        ta = total;
-        fetch(buf, p0, total, va);
-        if (!advance()) {
-          count(va, pa, ta);
-        } else {
-          pb = p0;
-          tb2 = total;
-          fetch(buf, p0, total, vb);
-          for (;;) {
-            if (!advance()) {
-              count(va, pa, ta);
-              count(vb, pb, tb2);
-              break;
-            }
-            pc = p0;
-            tc = total;
-            fetch(buf, p0, total, vc);
-            count(va, pa, ta);
-            if (!advance()) {
-              count(vb, pb, tb2);
-              count(vc, pc, tc);
-              break;
-            }
-            pa = p0;
-            ta = total;
-            fetch(buf, p0, total, va);
-            count(vb, pb, tb2);
-            if (!advance()) {
-              count(vc, pc, tc);
-              count(va, pa, ta);
-              break;
-            }
+        };
+        {
+          // three rotating piece buffers: the loads of steps i+1 and i+2 are in
+          // flight while step i counts (unrolled by 3, no register copies)
+          uint4 va[PPS], vb[PPS], vc[PPS];
+          uint32_t pa, ta, pb, tb2, pc, tc;
+          pa = p0;
+          ta = total;
+          fetch(buf, p0, total, va);
+          if (!advance()) {
+            step(va, pa, ta);
+          } else {
             pb = p0;
             tb2 = total;
             fetch(buf, p0, total, vb);
-            count(vc, pc, tc);
+            for (;;) {
+              if (!advance()) {
+                step(va, pa, ta);
+                step(vb, pb, tb2);
+                break;
+              }
+              pc = p0;
+              tc = total;
+              fetch(buf, p0, total, vc);
+              step(va, pa, ta);
+              if (!advance()) {
+                step(vb, pb, tb2);
+                step(vc, pc, tc);
+                break;
+              }
+              pa = p0;
+              ta = total;
+              fetch(buf, p0, total, va);
+              step(vb, pb, tb2);
+              if (!advance()) {
+                step(vc, pc, tc);
+                step(va, pa, ta);
+                break;
+              }
+              pb = p0;
+              tb2 = total;
+              fetch(buf, p0, total, vb);
+              step(vc, pc, tc);
+            }
           }
         }
       }
     }
-  }
+  };
   const uint32_t pcls = 8u * (uint32_t)((w0 + lane) & 7);
+  // pad / dead-lane keys of the run just walked → its correction bins
+  auto flush_corr = [&](uint32_t *cb) __attribute__((always_inline)) {
 #pragma unroll
-  for (int e = 1; e < 8; ++e)
-    if (padc[e]) atomicAdd(&corr[pcls + e], padc[e]);
-  if (dead) atomicAdd(&corr[lane], 8 * dead);
+    for (int e = 1; e < 8; ++e)
+      if (padc[e]) atomicAdd(&cb[pcls + e], padc[e]);
+    if (dead) atomicAdd(&cb[lane], 8 * dead);
+  };
+  walk(count);
+  flush_corr(corr);
+  if constexpr (PROBE) {
+#pragma unroll
+    for (int e = 1; e < 8; ++e) padc[e] = 0;
+    dead = 0;
+    __syncthreads();
+    // Finalise: every half is < 2^15 now and nothing adds any more, so a half
+    // may use all 16 bits.  A hot key's total T (slot total + remainder − its
+    // pad correction: taken from the 32-bit total, the half could borrow) is
+    // split: the half becomes T mod 2^16 — probed like any count, no flag, no
+    // test — and what is left (a multiple of 2^16, nonzero only from in-degree
+    // 2^16 up) makes the key one of the unit's few SPECIAL keys, whose probes
+    // phase 2 counts per wave.  Two hot keys can share a word: atomics.  A key
+    // found in the global log (hot table full) appends its remainder there
+    // and its half becomes 0xFFFF, the one reserved value (a hot key whose
+    // T mod 2^16 is 0xFFFF stores 0xFFFE and 1 more in its extra).
+    for (uint32_t sl = threadIdx.x; sl < pr.hotcap; sl += C5_BLOCK) {
+      const uint32_t h = hk[sl];
+      if (h == C5_HOT_EMPTY) continue;
+      const uint32_t sh = (h >> 15) << 4, wi = h & (C2_WORDS - 1);
+      const uint32_t half = (words[wi] >> sh) & 0xFFFFu;
+      const uint32_t t = hv[sl] + half - (h < (uint32_t)C5_CORR ? corr[h] : 0u);
+      uint32_t lo = t & 0xFFFFu;
+      if (lo == 0xFFFFu) lo = 0xFFFEu;
+      atomicAnd(&words[wi], ~(0xFFFFu << sh));
+      atomicOr(&words[wi], lo << sh);
+      if (h < (uint32_t)C5_CORR) atomicOr(&hotpad[h >> 5], 1u << (h & 31));
+      if (t != lo) {
+        const uint32_t i = atomicAdd(nspec, 1u);  // ≤ one per slot: i < C5_HOT
+        sk[i] = h;
+        sx[i] = t - lo;
+      }
+    }
+    const uint32_t ln = min(__hip_atomic_load(ovf.n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), ovf.cap);
+    for (uint32_t i = threadIdx.x; i < ln; i += C5_BLOCK) {
+      const uint2 en = c5_log_entry(ovf.log, i);
+      if (en.y == 0 || (en.x >> C2_BITS) != (uint32_t)u.run) continue;  // unwritten, or another unit's
+      const uint32_t key = en.x & 0xFFFFu, sh = (key >> 15) << 4, wi = key & (C2_WORDS - 1);
+      const uint32_t oh = (atomicOr(&words[wi], 0xFFFFu << sh) >> sh) & 0xFFFFu;
+      if (oh != 0xFFFFu) {  // the first of the key's entries met: its remainder (mod 2^32)
+        c5_log_append(ovf.log, ovf.n, ovf.cap, en.x, oh - (key < (uint32_t)C5_CORR ? corr[key] : 0u));
+        if (key < (uint32_t)C5_CORR) atomicOr(&hotpad[key >> 5], 1u << (key & 31));
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < C5_CORR && !((hotpad[threadIdx.x >> 5] >> (threadIdx.x & 31)) & 1u))
+      words[threadIdx.x] -= corr[threadIdx.x];  // plain pad bins: the half holds the pads too, no borrow
+    __syncthreads();
+    // Re-lay the halves as one uint16 per key (halves[key]): the probe's LDS
+    // address is then key·2, two VALU instead of five.  Through registers: every
+    // thread holds its 32 words across the barrier.
+    uint16_t *halves = (uint16_t *)words;
+    {
+      uint32_t wr[C2_WORDS / C5_BLOCK];
+#pragma unroll
+      for (int r = 0; r < C2_WORDS / C5_BLOCK; ++r) wr[r] = words[threadIdx.x + r * C5_BLOCK];
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < C2_WORDS / C5_BLOCK; ++r) {
+        halves[threadIdx.x + r * C5_BLOCK] = (uint16_t)wr[r];
+        halves[C2_WORDS + threadIdx.x + r * C5_BLOCK] = (uint16_t)(wr[r] >> 16);
+      }
+    }
+    __syncthreads();
+    // in[key] in full (cold: the pad-bin correction below)
+    const uint32_t ns = (uint32_t)__builtin_amdgcn_readfirstlane((int)*nspec);
+    auto full_in = [&](uint32_t key) -> uint32_t {
+      uint32_t t = halves[key];
+      if (t == 0xFFFFu) return c5_log_sum(ovf.log, ovf.n, ovf.cap, log_base + key);
+      for (uint32_t i = 0; i < ns; ++i) t += sk[i] == key ? sx[i] : 0u;
+      return t;
+    };
+    // Phase 2: Σ in[key] over the out-run's keys: per key one 16-bit LDS read
+    // (identical addresses broadcast), an add and a max.  R-MAT's in-hubs are
+    // out-hubs too (28 % of the hub bucket's out keys are the hub), so nothing
+    // here depends on how often a hot key is probed: a special key's probes are
+    // counted per wave with one compare and one ballot per key slot (the first
+    // two specials live in scalars, further ones are read from LDS per step)
+    // and count · extra is added at the end.
+    unsigned long long sum = 0, wsum = 0;  // per lane; per wave (uniform)
+    const uint32_t ks0 = ns > 0 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)sk[0]) : 0x10000u;
+    const uint32_t ks1 = ns > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)sk[1]) : 0x10000u;
+    uint32_t cn0 = 0, cn1 = 0;  // probes of specials 0 and 1 (uniform)
+    auto probe = [&](const uint4 *v, uint32_t p0, uint32_t total) __attribute__((always_inline)) {
+      uint32_t s32 = 0, mx = 0;  // 16 halves < 2^16: no overflow
+      uint32_t kk[PPS][8];
+#pragma unroll
+      for (int j = 0; j < PPS; ++j) {
+        const bool live = p0 + j * WAVE + lane < total;
+        dead += live ? 0u : 1u;
+        const uint32_t wd[4] = {live ? v[j].x : dead_keys.x, live ? v[j].y : dead_keys.y,
+                                live ? v[j].z : dead_keys.z, live ? v[j].w : dead_keys.w};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          kk[j][e] = (e & 1) ? wd[e >> 1] >> 16 : wd[e >> 1] & 0xFFFF;
+          const uint32_t h = halves[kk[j][e]];
+          s32 += h;
+          mx = max(mx, h);
+        }
+      }
+      sum += s32;
+      if (ns) {  // unit-uniform: this bucket has special keys
+#pragma unroll
+        for (int j = 0; j < PPS; ++j)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            cn0 += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(kk[j][e] == ks0));
+            if (ns > 1) cn1 += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(kk[j][e] == ks1));
+          }
+        for (uint32_t i = 2; i < ns; ++i) {
+          const uint32_t ks = (uint32_t)__builtin_amdgcn_readfirstlane((int)sk[i]);
+          uint32_t cn = 0;
+#pragma unroll
+          for (int j = 0; j < PPS; ++j)
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              cn += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(kk[j][e] == ks));
+          wsum += (unsigned long long)cn * (uint32_t)__builtin_amdgcn_readfirstlane((int)sx[i]);
+        }
+      }
+      if (__builtin_amdgcn_ballot_w64(mx == 0xFFFFu) != 0) {
+        // (hot table full) keys whose counts are in the global log: one copy of the scan
+        uint32_t lm = 0;
+#pragma unroll
+        for (int j = 0; j < PPS; ++j)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) lm |= halves[kk[j][e]] == 0xFFFFu ? 1u << (8 * j + e) : 0u;
+        while (lm) {
+          const uint32_t idx = (uint32_t)__builtin_ctz(lm);
+          lm &= lm - 1;
+          uint32_t key = 0;
+#pragma unroll
+          for (int j = 0; j < PPS; ++j)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) key = idx == (uint32_t)(8 * j + e) ? kk[j][e] : key;
+          sum += (unsigned long long)c5_log_sum(ovf.log, ovf.n, ovf.cap, log_base + key) - 0xFFFFu;
+        }
+      }
+    };
+    m = meta_t + (int64_t)(nb + u.run) * ntiles;  // out-run nb + b (run-major meta)
+    wpre = w0 + lane < w1 ? m[w0 + lane] : 0u;
+    walk(probe);
+    if (lane == 0) {
+      if (ns > 0) wsum += (unsigned long long)cn0 * sx[0];
+      if (ns > 1) wsum += (unsigned long long)cn1 * sx[1];
+      sum += wsum;
+    }
+    flush_corr(corr_out);
+    __syncthreads();
+    if (threadIdx.x < C5_CORR) {  // the out-run's pad / dead-lane keys were probed too
+      const uint32_t c = corr_out[threadIdx.x];
+      if (c) {
+        sum -= (unsigned long long)c * full_in(threadIdx.x);
+      }
+    }
+    // Epilogue (as k_chain2_dot_pairs): Σ and this unit's share of the
+    // self-loops, then the last unit to finish writes the count
+    const unsigned long long tot = block_reduce_sum(sum, red);
+    unsigned long long l = 0;
+    for (int64_t i = (int64_t)ui * C5_BLOCK + threadIdx.x; i < ntiles; i += (int64_t)nu * C5_BLOCK)
+      l += pr.tile_loops[i];
+    l = block_reduce_sum(l, red);
+    if (threadIdx.x == 0) {
+      if (tot) atomicAdd(pr.acc3, tot);
+      if (l) atomicAdd(pr.acc3 + 1, l);
+      __threadfence();
+      if (atomicAdd((unsigned int *)(pr.acc3 + 2), 1u) == (unsigned int)nu - 1) {
+        __threadfence();
+        const unsigned long long a0 = atomicAdd(pr.acc3, 0ull), a1 = atomicAdd(pr.acc3 + 1, 0ull);
+        // fin may be pinned host memory: a system-scope store
+        __hip_atomic_store(pr.fin, (int64_t)(a0 - a1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __threadfence_system();
+      }
+    }
+    return;
+  }
   if (zsplit && threadIdx.x == 0)
     while (!(__hip_atomic_load(&sd.claim[u.run], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) & (512 << u.slice)))
       __builtin_amdgcn_s_sleep(4);
@@ -992,12 +1307,14 @@ enum class C5Work {
 enum class C5Counters {
   U32,    // one uint32 per bin
   Pairs,  // exclusive units: packed uint16 pairs in the first half of the bucket; split runs uint32
-  Packed  // packed uint16 pairs, bucket b of slice k at (k·nb + b)·2^15 words
+  Packed, // packed uint16 pairs, bucket b of slice k at (k·nb + b)·2^15 words
+  Probed  // in side only, never stored: the unit probes them in LDS with its out keys
 };
 enum class C5Log {
   Overflow,  // k_c3_overflow adds the hand-offs to the histograms
   Dot,       // left to the fused dot kernel (C2Spill)
-  PackedDot  // left to k_c5_dot_packed
+  PackedDot, // left to k_c5_dot_packed
+  Unit       // hot-table overflow only, read back by the unit that wrote it (mode P: no dot)
 };
 struct C5Mode {
   C5Work work;
@@ -1014,6 +1331,8 @@ struct C5PostPlan {
   int64_t ntiles, rstride, nkeys;
   bool zeroed_by_p1;  // P1's workgroups clear the layout's zero prefix (else: a memset here)
   C5PostLayout layout;
+  uint32_t hotcap = C5_HOT;  // mode P: hot-table slots
+  bool probe() const { return mode.counters == C5Counters::Probed; }
 };
 
 // part / meta: P1's ntiles tiles of nr = 2·nb runs.  Histograms: S slices per
@@ -1027,6 +1346,7 @@ struct C5PostBufs {
   BufPtr acc;
   const uint32_t *tile_loops;
   unsigned long long *acc3;
+  int64_t *fin = nullptr;  // mode P: where the last unit writes the count
 };
 
 // What the dot after c5_post reads: the hand-off log, the split flags (per
@@ -1069,11 +1389,21 @@ static C5PostPlan c5_plan_fused(int nb, int64_t ntiles, int64_t rstride, int64_t
   // write-back that T used to).  CAPF_C5_DIRECT=0 keeps the transpose pipeline.
   const char *de = getenv("CAPF_C5_DIRECT");
   const bool direct_env = !(de && atoi(de) == 0), one_slice = c5_slices(2 * nb) == 1;
+  // Mode P (one unit per bucket: in-run counted, out-run probed, no dot): the
+  // default when its nb units fill the GPU (≥ 256 buckets: s24 and up; at 128
+  // buckets it would leave half the CUs idle).  CAPF_C5_PROBE=1 / 0 forces it
+  // on (whenever S = 1) / off.  CAPF_C5_HOTCAP (tests): hot-table slots.
+  const char *pe = getenv("CAPF_C5_PROBE");
+  const bool probe = pe ? atoi(pe) != 0 : nb >= 256;
   const C5Mode m = !to_dot     ? C5Mode{C5Work::Units, C5Counters::U32, C5Log::Overflow}  // D
                    : !one_slice ? C5Mode{C5Work::Units, C5Counters::U32, C5Log::Dot}      // C: k_c5_fold sums the slices
-                   : direct_env ? C5Mode{C5Work::Direct, C5Counters::Pairs, C5Log::Dot}   // A: the default at ≥ 256 runs
-                                : C5Mode{C5Work::Units, C5Counters::Pairs, C5Log::Dot};   // B
-  return c5_plan(m, nb, ntiles, 0, ntiles, rstride, nkeys, true);
+                   : !direct_env ? C5Mode{C5Work::Units, C5Counters::Pairs, C5Log::Dot}   // B
+                   : probe       ? C5Mode{C5Work::Direct, C5Counters::Probed, C5Log::Unit}  // P: the default at ≥ 256 buckets
+                                 : C5Mode{C5Work::Direct, C5Counters::Pairs, C5Log::Dot};   // A: the default at 128 buckets
+  C5PostPlan p = c5_plan(m, nb, ntiles, 0, ntiles, rstride, nkeys, true);
+  const char *hc = getenv("CAPF_C5_HOTCAP");
+  if (hc) p.hotcap = (uint32_t)std::min(C5_HOT, std::max(1, atoi(hc)));
+  return p;
 }
 
 // A node-partitioned rank: tiles [0, t_in) hold the in side, [t_in, ntiles)
@@ -1097,6 +1427,8 @@ static C5PostOut c5_post(Session *s, const C5PostBufs &b, const C5PostPlan &p) {
   if (!attr_set) {
     HIP_CHECK(hipFuncSetAttribute((const void *)k_c5_gather<C5_PPS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   C5_GATHER_LDS));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_c5_gather<C5_PPS, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  C5_PROBE_LDS));
     attr_set = true;
   }
   char *base = (char *)b.acc->p;
@@ -1140,11 +1472,13 @@ static C5PostOut c5_post(Session *s, const C5PostBufs &b, const C5PostPlan &p) {
     // (folding the dot into P3's epilogue measured 0.51 ms for P3 against
     // 0.44 + 0.027 ms + a ~10 µs boundary: the dot kernel runs after P3)
     KernelTimer kt(s, "c5_gather", 2.0 * p.nkeys);
-    const int grid = listed ? l.max_units : (nr * p.S + 255) / 256 * 256;
-    hipLaunchKernelGGL(k_c5_gather<C5_PPS>, dim3((unsigned)grid), dim3(C5_BLOCK), C5_GATHER_LDS, s->stream,
+    const int grid = listed ? l.max_units : ((p.probe() ? p.sides.nb : nr * p.S) + 255) / 256 * 256;
+    const C5Probe pr{b.acc3, b.fin, b.tile_loops, p.hotcap};
+    auto kern = p.probe() ? k_c5_gather<C5_PPS, true> : k_c5_gather<C5_PPS, false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C5_BLOCK), p.probe() ? C5_PROBE_LDS : C5_GATHER_LDS, s->stream,
                        listed ? (const C3Unit *)units : nullptr, (const int32_t *)nunits, b.part,
                        listed ? (const uint32_t *)meta_t->p : b.meta, p.ntiles, p.sides.nb, p.rstride, b.h_in,
-                       b.h_out, p.slice_stride, out.ovf, sdk, p.S, p.mstride);
+                       b.h_out, p.slice_stride, out.ovf, sdk, p.S, p.mstride, pr);
     KERNEL_CHECK();
   }
   if (p.mode.log == C5Log::Overflow) {
@@ -1282,7 +1616,8 @@ static void chain2_c5(Session *s, C5Cols<W> c, bool in_range, uint32_t *h_in, ui
   const C5PostPlan plan = c5_plan_fused(c.nb, c.ntiles, c.rstride, 2 * c.n, spill != nullptr);
   const bool direct = plan.mode.work == C5Work::Direct;
   C5PostBufs bufs{(const uint16_t *)part->p,   (const uint32_t *)meta->p, h_in, h_out,
-                  s->alloc(plan.layout.bytes), (const uint32_t *)tl->p,   d_acc3};
+                  s->alloc(plan.layout.bytes), (const uint32_t *)tl->p,   d_acc3,
+                  spill ? spill->fin : nullptr};
   {
     KernelTimer kt(s, "c5_partition", (2.0 * W + 4.0) * c.n);
     const bool alias = c.u2 == c.u1 && c.v2 == c.v1;
@@ -1310,6 +1645,12 @@ static void chain2_c5(Session *s, C5Cols<W> c, bool in_range, uint32_t *h_in, ui
     spill->nb = c.nb;
     spill->tile_loops = direct ? bufs.tile_loops : nullptr;  // (direct: no transpose summed them)
     spill->ntiles = direct ? c.ntiles : 0;
+  }
+  if (plan.probe()) {  // the last P3 unit wrote the count: no dot; the log is diagnostics only
+    spill->log = out.ovf.log;
+    spill->n = out.ovf.n;
+    spill->cap = out.ovf.cap;
+    spill->fin_written = true;
   }
   if (plan.S > 1) {
     hipLaunchKernelGGL(k_c5_fold, dim3(grid_for(plan.slice_stride / 4, 256, 1024)), dim3(256), 0, s->stream,

@@ -1435,7 +1435,9 @@ static bool run_chain2(Session *s, const JoinGraph &g, const Chain2 &c, uint64_t
         KERNEL_CHECK();
       }
     }
-    {
+    if (spill.fin_written) {  // P3's last unit wrote the count
+      fin_done = true;
+    } else {
       KernelTimer kt(s, "chain2_dot", 8.0 * dot_len);
       // one block per CU (s24: 256 blocks 24 µs, 2048 37 µs — same-address atomics)
       unsigned grid = grid_for(dot_len / 4 + 1, 256, dot_grid(s->num_cus));
