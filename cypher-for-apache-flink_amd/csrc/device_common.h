@@ -25,6 +25,26 @@ __host__ __device__ inline uint64_t fmix64(uint64_t k) {
   return k;
 }
 
+// Canonical key bits of a FLOAT ("Ordering and equality of
+// values"): -0.0 → 0.0 and every NaN, of any sign or payload, → one pattern,
+// so keys hash, compare and group as the values do.
+__host__ __device__ inline uint64_t f64_key_bits(uint64_t b) {
+  if ((b & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull) return 0x7FF8000000000000ull;
+  return b == 0x8000000000000000ull ? 0 : b;
+}
+
+// Order-preserving uint64 image of the canonical bits: unsigned order of the
+// images = −∞ < … < 0.0 < … < +∞ < NaN (java.lang.Double.compare, ±0.0 equal).
+__host__ __device__ inline uint64_t f64_order_key(uint64_t b) {
+  b = f64_key_bits(b);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// The canonical bits back from their order image.
+__host__ __device__ inline uint64_t f64_order_key_bits(uint64_t k) {
+  return (k >> 63) ? (k ^ 0x8000000000000000ull) : ~k;
+}
+
 // Bijective mixer of node offsets on a 2^k domain: odd multiply mod 2^k, then
 // xorshift (each step invertible).  The radix-partitioned histograms key
 // their runs by the HIGH bits of node_mix(id − lo): hash partitioning, so the

@@ -33,11 +33,10 @@ __device__ inline uint64_t key_word(const ColView &c, int64_t r, bool &isnull) {
   isnull = false;
   if (c.type == CAPF_TYPE_BOOL) return ((const uint8_t *)c.data)[r] ? 1 : 0;
   if (c.type != CAPF_TYPE_FLOAT64) return (uint64_t)ld_int(c, r);
-  uint64_t w = ((const uint64_t *)c.data)[r];
-  if (w == 0x8000000000000000ull) w = 0;  // -0.0 == 0.0
-  return w;
+  return f64_key_bits(((const uint64_t *)c.data)[r]);  // -0.0 == 0.0, every NaN one key
 }
 
+// (oracle/rowhash.py restates this for one non-NULL INTEGER column: change both)
 __device__ inline uint64_t hash_row(const ColView *cols, int n, int64_t r, bool &anynull) {
   uint64_t h = 0x243F6A8885A308D3ull;
   anynull = false;
@@ -418,26 +417,9 @@ __device__ inline T load_num(const ColView &c, int64_t r) {
   return (T)ld_int(c, r);
 }
 
-__device__ inline void atomic_min_f64(double *p, double v) {
-  unsigned long long *a = (unsigned long long *)p;
-  unsigned long long old = *a;
-  while (v < __longlong_as_double(old)) {
-    unsigned long long prev = atomicCAS(a, old, (unsigned long long)__double_as_longlong(v));
-    if (prev == old) break;
-    old = prev;
-  }
-}
-__device__ inline void atomic_max_f64(double *p, double v) {
-  unsigned long long *a = (unsigned long long *)p;
-  unsigned long long old = *a;
-  while (v > __longlong_as_double(old)) {
-    unsigned long long prev = atomicCAS(a, old, (unsigned long long)__double_as_longlong(v));
-    if (prev == old) break;
-    old = prev;
-  }
-}
-
-// acc: per group value (int64 or double), cnt: per group non-null count
+// acc: per group value (int64 or double), cnt: per group non-null count.
+// min / max over FLOAT accumulate the order image (f64_order_key) with integer
+// atomics — the total order, NaN the largest value; k_agg_final maps it back.
 __global__ void k_agg(const int64_t *gid, int64_t n, ColView arg, int kind, int fl, void *acc,
                       unsigned long long *cnt) {
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n;
@@ -452,11 +434,14 @@ __global__ void k_agg(const int64_t *gid, int64_t n, ColView arg, int kind, int 
     atomicAdd(&cnt[g], 1ull);
     if (kind == CAPF_AGG_COUNT) continue;
     if (fl) {
-      double v = load_num<double>(arg, r);
-      double *a = (double *)acc + g;
-      if (kind == CAPF_AGG_SUM || kind == CAPF_AGG_AVG) atomicAdd(a, v);
-      else if (kind == CAPF_AGG_MIN) atomic_min_f64(a, v);
-      else atomic_max_f64(a, v);
+      if (kind == CAPF_AGG_SUM || kind == CAPF_AGG_AVG) {
+        atomicAdd((double *)acc + g, load_num<double>(arg, r));
+      } else {
+        const unsigned long long k = f64_order_key(((const uint64_t *)arg.data)[r]);
+        unsigned long long *a = (unsigned long long *)acc + g;
+        if (kind == CAPF_AGG_MIN) atomicMin(a, k);
+        else atomicMax(a, k);
+      }
     } else {
       long long v = load_num<long long>(arg, r);
       long long *a = (long long *)acc + g;
@@ -481,6 +466,8 @@ __global__ void k_agg_final(int64_t ng, int kind, int fl, int out_type, const vo
     if (out_type == CAPF_TYPE_NULL) continue;
     if (fl) {
       double a = ((const double *)acc)[g];
+      if (kind == CAPF_AGG_MIN || kind == CAPF_AGG_MAX)
+        a = __longlong_as_double((long long)f64_order_key_bits(((const uint64_t *)acc)[g]));
       if (kind == CAPF_AGG_AVG && c > 0) a = a / (double)c;
       if (out_type == CAPF_TYPE_FLOAT64)
         ((double *)out)[g] = c > 0 ? a : 0.0;
@@ -760,9 +747,7 @@ __global__ void k_pct_keys(const int64_t *gid, ColView arg, int64_t n, int64_t n
     gkey[r] = (uint64_t)g;
     uint64_t k;
     if (arg.type == CAPF_TYPE_FLOAT64) {
-      uint64_t b = ((const uint64_t *)arg.data)[r];
-      if (b == 0x8000000000000000ull) b = 0;
-      k = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+      k = f64_order_key(((const uint64_t *)arg.data)[r]);  // Scala's Double ordering: NaN last
     } else {
       k = (uint64_t)ld_int(arg, r) ^ 0x8000000000000000ull;
     }
@@ -870,11 +855,8 @@ ColPtr aggregate(Session *s, const Grouping &g, const Data &d, int64_t nrows, in
   HIP_CHECK(hipMemsetAsync(cnt->p, 0, 8 * ng, s->stream));
   // identity element of the accumulator
   int64_t init_bits = 0;
-  if (kind == CAPF_AGG_MIN) {
-    if (fl) { double x = INFINITY; memcpy(&init_bits, &x, 8); } else init_bits = INT64_MAX;
-  } else if (kind == CAPF_AGG_MAX) {
-    if (fl) { double x = -INFINITY; memcpy(&init_bits, &x, 8); } else init_bits = INT64_MIN;
-  }
+  if (kind == CAPF_AGG_MIN) init_bits = fl ? -1 : INT64_MAX;  // (FLOAT: the order image, 2^64 − 1 / 0)
+  else if (kind == CAPF_AGG_MAX) init_bits = fl ? 0 : INT64_MIN;
   hipLaunchKernelGGL(k_fill_i64, dim3(grid_for(ng, 256)), dim3(256), 0, s->stream,
                      (int64_t *)acc->p, init_bits, ng);
   KERNEL_CHECK();
@@ -904,9 +886,7 @@ __global__ void k_sort_key(ColView c, int64_t n, int desc, uint64_t *key, uint64
       if (c.type == CAPF_TYPE_BOOL) {
         k = ((const uint8_t *)c.data)[r] ? 1 : 0;
       } else if (c.type == CAPF_TYPE_FLOAT64) {
-        uint64_t b = ((const uint64_t *)c.data)[r];
-        if (b == 0x8000000000000000ull) b = 0;
-        k = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+        k = f64_order_key(((const uint64_t *)c.data)[r]);  // … < +∞ < NaN (every NaN one value)
       } else {
         k = (uint64_t)ld_int(c, r) ^ 0x8000000000000000ull;
       }

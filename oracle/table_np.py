@@ -681,7 +681,7 @@ def _exact_stdev(vals, samp):
 def _percentile(vals, p, cont):
     """PercentileUdafs.scala:59-96 (the Spark backend's UDAFs): over the
     ascending values as doubles."""
-    sv = sorted(vals)
+    sv = sorted(vals, key=_total_key)  # Scala's Double ordering: NaN last
     n = len(sv)
     if n == 0:
         return None
@@ -702,6 +702,37 @@ def _percentile(vals, p, cont):
     return (1 - w) * sv[succ - 1] + w * sv[prec - 1]
 
 
+_NAN_BITS = np.uint64(0x7FF8000000000000)
+
+
+def _float_key_bits(f):
+    """Canonical key bits of FLOAT values (ordering and equality):
+    -0.0 → 0.0 and every NaN, of any sign or payload, → one pattern."""
+    f = np.asarray(f, dtype=np.float64)
+    b = np.where(f == 0, 0.0, f).view(np.uint64).copy()
+    b[np.isnan(f)] = _NAN_BITS
+    return b
+
+
+def _float_order_key(f):
+    """Order-preserving uint64 image of the canonical bits: the total order
+    −∞ < … < −0.0 = 0.0 < … < +∞ < NaN (java.lang.Double.compare, ±0 equal)."""
+    b = _float_key_bits(f)
+    return np.where((b >> np.uint64(63)) != 0, ~b, b | np.uint64(1 << 63))
+
+
+def _total_key(x):
+    """Python sort key of one non-NULL value under the same total order."""
+    return (x != x, 0.0 if x != x else x) if isinstance(x, float) else (False, x)
+
+
+def _canon(x):
+    """One hashable representative per key value (all NaNs one, ±0.0 one)."""
+    if isinstance(x, float):
+        return "NaN" if x != x else x + 0.0
+    return x
+
+
 def _key_codes(cols, null_is_group=True):
     """Joint integer codes of rows over `cols` (NULL → its own code, or -1)."""
     n = len(cols[0].ok) if cols else 0
@@ -717,8 +748,7 @@ def _key_codes(cols, null_is_group=True):
             parts.append(np.asarray(inv, dtype=np.int64))
         elif c.t == T_FLOAT:
             f = np.where(c.ok, c.v.astype(np.float64), 0.0)
-            f = np.where(f == 0, 0.0, f)  # -0.0 == 0.0
-            parts.append(f.view(np.int64))
+            parts.append(_float_key_bits(f).view(np.int64))  # -0.0 == 0.0, NaN == NaN
         else:
             parts.append(np.where(c.ok, c.v.astype(np.int64), 0))
         parts.append(c.ok.astype(np.int64))
@@ -871,9 +901,10 @@ class OracleTable:
                 enc = [x.encode("utf-16-be", "surrogatepass") if p else b"" for x, p in zip(vals, ok)]
                 rank = {k: i for i, k in enumerate(sorted(set(enc)))}
                 vals = np.array([rank[k] for k in enc], dtype=np.int64)
-            key = vals.astype(np.float64) if v.t == T_FLOAT else vals.astype(np.int64)
-            if desc:
-                key = -key if v.t == T_FLOAT else ~key
+            key = _float_order_key(vals) if v.t == T_FLOAT else vals.astype(np.int64)
+            if desc:  # the exact reverse of the ascending total order
+                key = ~key
+            key = np.where(ok, key, 0)  # NULLs tie (input order kept) whatever lies under them
             o1 = np.argsort(key, kind="stable")
             idx = idx[o1]
             ok = ok[o1]
@@ -955,8 +986,8 @@ class OracleTable:
                 seen = set()
                 cnt = np.zeros(ng, np.int64)
                 for g, x, ok in zip(gid.tolist(), v.v.tolist(), sel.tolist()):
-                    if ok and (g, x) not in seen:
-                        seen.add((g, x))
+                    if ok and (g, _canon(x)) not in seen:
+                        seen.add((g, _canon(x)))
                         cnt[g] += 1
                 return Col(T_INT, cnt, np.ones(ng, bool))
             return Col(T_INT, np.bincount(gid[sel], minlength=ng).astype(np.int64), np.ones(ng, bool))
@@ -1002,9 +1033,9 @@ class OracleTable:
             if agg.kind in (AGG_SUM, AGG_AVG):
                 acc[g] = x if a is None else a + x
             elif agg.kind == AGG_MIN:
-                acc[g] = x if a is None or x < a else a
+                acc[g] = x if a is None or _total_key(x) < _total_key(a) else a
             else:
-                acc[g] = x if a is None or x > a else a
+                acc[g] = x if a is None or _total_key(x) > _total_key(a) else a
         for g in range(ng):
             a = acc[g]
             if a is None:
