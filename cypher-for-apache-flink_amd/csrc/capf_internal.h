@@ -584,14 +584,20 @@ int32_t record_error(int32_t code, const char *msg);
 bool try_fused_count(const NodePtr &n, int64_t *out);
 // Config 5 below the SPI: Group(a; count(*)) over Distinct(a, b) over the
 // UNION ALL of the var-length join chains k = 1..u (fused_count.hip) →
-// the (a-keys, reach) rows by multi-source BFS; false: not that shape.
+// the (a-keys, reach) rows by multi-source BFS; chains k = l..u with
+// 2 ≤ l ≤ u ≤ 4 and all their NOT(e_i = e_j) filters → by trail
+// enumeration; false: not that shape.
 bool try_fused_reach(const NodePtr &grp, DataPtr &out);
 // Multi-source BFS reach (var_length_reach.hip): rows (a, #targets reachable
 // by a walk of length 1..upper) for every source reaching one; include_self
 // (lower bound 0): every source, (a, a) counted once whatever its labels.
+// lower ≥ 2 (≤ upper ≤ 4): #targets joined by a trail of length lower..upper,
+// by per-source trail enumeration over an out-CSR (each row of the rel table
+// one rel); nullptr when the id dictionary exceeds the kernel's LDS bitmap
+// (2^20 nodes, CAPF_VT_MAX_NODES lowers it) — the caller runs the join chain.
 DataPtr var_length_reach_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m,
-                              const ColPtr &sid, int64_t ns_in, const ColPtr &tid, int64_t nt, int upper,
-                              bool include_self = false);
+                              const ColPtr &sid, int64_t ns_in, const ColPtr &tid, int64_t nt, int lower,
+                              int upper);
 // Radix-partitioned LDS histograms of the 2-hop count (chain2_partitioned.hip).
 // cols = {start(r1), end(r1), start(r2), end(r2)}, all plain or all FOR32.
 // Histograms hold chain2_hist_len(hi − lo + 1) counters indexed by

@@ -1723,6 +1723,7 @@ struct ReachShape {
   Leaf sa, sb, rel;
   int x = -1, y = -1, cs = -1, cd = -1;  // S_a / S_b id columns, rel start / end columns
   int k = 0;                              // rel leaves in the chain
+  bool all_neq = false;                   // every pair of them carries NOT(e_i = e_j), on one column
   std::vector<RCol> roles;                // per tracked column
 };
 
@@ -1775,6 +1776,7 @@ static bool reach_branch(const ReachBranch &br, const std::vector<int> &a_cols, 
   seen[la] = 1;
   sh.k = 0;
   sh.cs = entry;
+  std::vector<int> pos(L, -1);  // leaf → its place among the chain's rel leaves
   for (;;) {
     if (cur < 0 || seen[cur]) return reach_reject("branch check 8");
     seen[cur] = 1;
@@ -1793,6 +1795,7 @@ static bool reach_branch(const ReachBranch &br, const std::vector<int> &a_cols, 
     if (out.first == entry) return reach_reject("branch check 12");
     if (sh.k == 0) sh.cd = out.first;
     else if (out.first != sh.cd) return reach_reject("branch check 13");
+    pos[cur] = sh.k;
     ++sh.k;
     prev = cur;
     cur = out.second.leaf;
@@ -1804,13 +1807,31 @@ static bool reach_branch(const ReachBranch &br, const std::vector<int> &a_cols, 
   sh.sb = g.leaves[lb];
   if (sh.sa.node == sh.rel.node || sh.sb.node == sh.rel.node) return reach_reject("branch check 16");
   if (!sh.rel.col_eqs.empty() || !sh.sa.col_eqs.empty() || !sh.sb.col_eqs.empty()) return reach_reject("branch check 17");
-  // isomorphism filters: NOT(e_i = e_j) on one unique rel column
+  // isomorphism filters: NOT(e_i = e_j) on one unique rel column.  Walks
+  // (lower bound ≤ 1) need none of them; for trails they are the semantics,
+  // so all_neq records whether all k(k−1)/2 pairs are there, on one column.
+  std::vector<char> pair_seen((size_t)sh.k * sh.k, 0);
+  int npairs = 0, neq_col = -1;
+  bool one_col = true;
   for (auto &ne : g.neqs) {
     if (ne.first.leaf == ne.second.leaf || ne.first.col != ne.second.col) return reach_reject("branch check 18");
     if (ne.first.leaf == la || ne.first.leaf == lb || ne.second.leaf == la || ne.second.leaf == lb)
       return reach_reject("branch check 19");
     if (!column_unique(sh.rel.node, ne.first.col)) return reach_reject("branch check 20");
+    if (neq_col < 0) neq_col = ne.first.col;
+    one_col &= ne.first.col == neq_col;
+    if (ne.first.leaf < 0 || ne.second.leaf < 0 || pos[ne.first.leaf] < 0 || pos[ne.second.leaf] < 0) {
+      one_col = false;
+      continue;
+    }
+    const int i = std::min(pos[ne.first.leaf], pos[ne.second.leaf]);
+    const int j = std::max(pos[ne.first.leaf], pos[ne.second.leaf]);
+    if (!pair_seen[(size_t)i * sh.k + j]) {
+      pair_seen[(size_t)i * sh.k + j] = 1;
+      ++npairs;
+    }
   }
+  sh.all_neq = one_col && npairs == sh.k * (sh.k - 1) / 2;
   // roles of the tracked columns
   sh.roles.assign(br.cols.size(), RCol{});
   for (size_t i = 0; i < br.cols.size(); ++i) {
@@ -1895,9 +1916,15 @@ bool try_fused_reach(const NodePtr &grp, DataPtr &result) {
       if (r.role == 2 && !prog_eq(r.lit, r0.lit)) return reach_reject("literals differ across branches");
     }
   }
-  const int upper = 64 - __builtin_clzll(lengths);
-  if (lengths != (upper == 64 ? ~uint64_t(0) : (uint64_t(1) << upper) - 1))
-    return reach_reject("lengths are not 1..u");
+  const int upper = 64 - __builtin_clzll(lengths), lower = __builtin_ctzll(lengths) + 1;
+  if ((lengths >> (lower - 1)) != (upper - lower == 63 ? ~uint64_t(0) : (uint64_t(1) << (upper - lower + 1)) - 1))
+    return reach_reject("lengths are not l..u");
+  if (lower >= 2) {  // trails (var_length_reach.hip::k_vt_trails)
+    if (zero >= 0) return reach_reject("a zero-length branch beside lengths from 2");
+    if (upper > 4) return reach_reject("trail lengths above 4");
+    for (auto &sh : shapes)
+      if (!sh.all_neq) return reach_reject("a branch lacks some NOT(e_i = e_j) filters: not a trail");
+  }
   const ReachShape &sh = shapes[0];
   // DISTINCT over (a, b): both ids among its keys, every key a column of S_a /
   // S_b or a literal; group keys: S_a columns (with the id) or literals
@@ -1949,8 +1976,9 @@ bool try_fused_reach(const NodePtr &grp, DataPtr &result) {
   }
   if (lr.data->nrows >= (int64_t(1) << 32)) return reach_reject("more than 2^32 rels");
   DataPtr res = var_length_reach_rows(s, rs, rd, lr.data->nrows, xa, la.data->nrows, yb,
-                                      lb.data->nrows, upper, zero >= 0);
-  s->last_plan = "fused_var_length_reach";
+                                      lb.data->nrows, zero >= 0 ? 0 : lower, upper);
+  if (!res) return reach_reject("more nodes than the trail kernel's LDS bitmap holds");
+  s->last_plan = lower >= 2 ? "fused_var_length_trails" : "fused_var_length_reach";
   // output: group keys (a's id, other S_a columns gathered by a's row, literals)
   // then one reach column per count(*)
   const int64_t nr = res->nrows;

@@ -28,6 +28,9 @@
 //          popcount → reach of source 64k + j
 // Sources are processed in batches of 64·K so the three state arrays stay
 // within a fixed HBM budget.  Bytes per level ≈ 8·K·(M + 3·D).
+//
+// Lower bound ≥ 2 (≤ upper ≤ 4) is answered by trail enumeration instead:
+// k_vt_trails below ("trails").
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -274,6 +277,178 @@ __global__ void k_vr_pos(const int64_t *reach, int64_t n, uint8_t *flag) {
     flag[i] = reach[i] > 0;
 }
 
+// ------------------------------------------------------------------ trails
+// Lower bound ≥ 2 (directed, upper ≤ 4): the DISTINCT (a, b) pairs are those
+// joined by a TRAIL (pairwise distinct rels) of length lower..upper — a walk
+// no longer shortens into the range (a→b, b→a: *2..3 has the walk a→b→a→b and
+// no trail to b), so the BFS above cannot answer it.  One workgroup per source
+// enumerates the source's trails over an out-CSR whose positions are the rel
+// identities (one position per rel row: parallel rels differ, a self-loop is
+// one) and marks their end nodes in a D-bit LDS bitmap; reach = popcount of
+// bitmap ∧ target mask.
+constexpr int VT_BLOCK = 512;
+constexpr uint32_t VT_NONE = 0xFFFFFFFFu;          // an empty stack entry (no rel position: m < 2^31)
+constexpr int64_t VT_MAX_NODES = int64_t(1) << 20;  // a 128 KiB bitmap of the CU's 160 KiB LDS
+constexpr size_t VT_LDS_MAX = 160 * 1024;
+constexpr int VT_ILP = 4;            // independent row loads per lane
+constexpr uint32_t VT_SHORT = 32;    // last-level rows up to this length are walked by one lane each
+
+__global__ void k_vt_tmask(const uint8_t *tflag, uint32_t D, uint32_t *tmask) {
+  const uint32_t W = (D + 31) / 32;
+  for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < W; w += gridDim.x * blockDim.x) {
+    uint32_t v = 0;
+    for (uint32_t b = 0; b < 32 && w * 32 + b < D; ++b) v |= (tflag[w * 32 + b] ? 1u : 0u) << b;
+    tmask[w] = v;
+  }
+}
+
+// sources by decreasing out-degree: a hub source's workgroup starts first
+__global__ void k_vt_srckey(const int64_t *src_nodes, int64_t ns, const uint32_t *orow, uint64_t *key) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < ns;
+       j += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t a = src_nodes[j];
+    key[j] = ((uint64_t)(0xFFFFFFFFu - (orow[a + 1] - orow[a])) << 32) | (uint64_t)j;
+  }
+}
+
+__device__ inline void vt_mark(uint32_t *bm, uint32_t y) { atomicOr(&bm[y >> 5], 1u << (y & 31)); }
+
+// The wave stands at node d_S with out-row [b, e) after a trail of S rels whose
+// positions are s1..s3 (VT_NONE beyond S) and whose start nodes are d0..d_{S-1}
+// (VT_NONE beyond d_S); everything but `lane` is wave-uniform.  Last level
+// (S + 1 = U): lanes stride over the row, skip the stack's positions and mark
+// the end nodes.  Before it: each lane takes one position of the row, loads
+// its end node y and y's row bounds, marks y when the trail is long enough,
+// and the wave descends into the lanes' rows one after the other (bounds
+// handed out by readlane).
+// Expanded rows (ex, a second bitmap): when y's row is the last level and y is
+// none of d0..d_S, no rel of the stack lies in y's row, so what the last level
+// marks from y is y's whole row, whatever trail led there: the lane that sets
+// y's bit in ex first descends, every later visit of y from this source is
+// dropped.  A hub source reaches the same nodes over 10^7 trail prefixes; its
+// last level shrinks from one row per prefix to one row per node.
+template <int S, int U>
+__device__ inline void vt_walk(const uint32_t *__restrict__ orow, const uint32_t *__restrict__ ocol,
+                               uint32_t *bm, uint32_t *ex, int lower, uint32_t b, uint32_t e,
+                               uint32_t s1, uint32_t s2, uint32_t s3, uint32_t d0, uint32_t d1,
+                               uint32_t d2, uint32_t d3, int lane) {
+  if constexpr (S + 1 >= U) {
+    // VT_ILP loads in flight per lane: a long row is a chain of load → LDS or otherwise
+    for (uint32_t p0 = b + lane; p0 < e; p0 += VT_ILP * WAVE) {
+      uint32_t v[VT_ILP];
+      bool on[VT_ILP];
+#pragma unroll
+      for (int i = 0; i < VT_ILP; ++i) {
+        const uint32_t p = p0 + i * WAVE;
+        on[i] = p < e && p != s1 && p != s2 && p != s3;
+        v[i] = on[i] ? ocol[p] : 0u;
+      }
+#pragma unroll
+      for (int i = 0; i < VT_ILP; ++i)
+        if (on[i]) vt_mark(bm, v[i]);
+    }
+  } else {
+    for (uint32_t p0 = b; p0 < e; p0 += WAVE) {
+      const uint32_t p = p0 + lane;
+      const bool ok = p < e && p != s1 && p != s2 && p != s3;
+      uint32_t y = 0, yb = 0, ye = 0;
+      if (ok) {
+        y = ocol[p];
+        yb = orow[y];
+        ye = orow[y + 1];
+        if (S + 1 >= lower) vt_mark(bm, y);
+        if constexpr (S + 2 == U) {
+          if (ex && ye > yb && y != d0 && y != d1 && y != d2 && y != d3) {
+            const uint32_t bit = 1u << (y & 31);
+            if (atomicOr(&ex[y >> 5], bit) & bit) ye = yb;  // y's row is already in the bitmap
+          }
+        }
+      }
+      if constexpr (S + 2 == U) {
+        // short last-level rows: every lane walks its own y's row (stack: s1..s3
+        // and p, the rel that led to y) — 64 rows at a time, instead of the
+        // wave descending into one row of a few entries after the other
+        const uint32_t len = ok ? ye - yb : 0u;
+        const bool mine = len > 0 && len <= VT_SHORT;
+        for (uint32_t k = 0; __ballot(mine && k < len); k += VT_ILP) {
+          uint32_t v[VT_ILP];
+          bool on[VT_ILP];
+#pragma unroll
+          for (int i = 0; i < VT_ILP; ++i) {
+            const uint32_t pp = yb + k + i;
+            on[i] = mine && k + i < len && pp != s1 && pp != s2 && pp != s3 && pp != p;
+            v[i] = on[i] ? ocol[pp] : 0u;
+          }
+#pragma unroll
+          for (int i = 0; i < VT_ILP; ++i)
+            if (on[i]) vt_mark(bm, v[i]);
+        }
+        if (mine) ye = yb;
+      }
+      unsigned long long todo = __ballot(ok && ye > yb);
+      while (todo) {
+        const int i = __builtin_amdgcn_readfirstlane(__ffsll(todo) - 1);
+        todo &= todo - 1;
+        const uint32_t nb = __builtin_amdgcn_readlane(yb, i), ne = __builtin_amdgcn_readlane(ye, i);
+        const uint32_t ny = __builtin_amdgcn_readlane(y, i);
+        const uint32_t q = p0 + (uint32_t)i;
+        if constexpr (S == 1) vt_walk<2, U>(orow, ocol, bm, ex, lower, nb, ne, s1, q, VT_NONE, d0, d1, ny, VT_NONE, lane);
+        else vt_walk<3, U>(orow, ocol, bm, ex, lower, nb, ne, s1, s2, q, d0, d1, d2, ny, lane);
+      }
+    }
+  }
+}
+
+// Block blockIdx.x = the source sorder[blockIdx.x] (low word: its position j
+// in src_nodes).  Dynamic LDS: the bitmap (⌈D/32⌉ words, padded to 16 B), the
+// expanded-rows bitmap of the same size when use_ex, then the first-hop cursor
+// and the count.  The waves take first hops from the cursor (wave-uniform
+// loads), so a hub source's rows spread over all waves.
+template <int U>
+__global__ __launch_bounds__(VT_BLOCK) void k_vt_trails(const uint32_t *__restrict__ orow,
+                                                        const uint32_t *__restrict__ ocol,
+                                                        const uint64_t *__restrict__ sorder,
+                                                        const int64_t *__restrict__ src_nodes,
+                                                        const uint32_t *__restrict__ tmask, uint32_t D,
+                                                        int lower, int use_ex, int64_t *reach) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t vt_lds[];
+  const uint32_t W = (D + 31) / 32, Wp = (W + 3) & ~3u;
+  uint32_t *bm = vt_lds, *ex = use_ex ? vt_lds + Wp : nullptr;
+  uint32_t *ctl = vt_lds + (use_ex ? 2 * Wp : Wp);
+  for (uint32_t w = threadIdx.x; w < (use_ex ? 2 * Wp : Wp); w += VT_BLOCK) vt_lds[w] = 0;
+  if (threadIdx.x < 2) ctl[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t j = (int64_t)(uint32_t)sorder[blockIdx.x];
+  const uint32_t a = (uint32_t)src_nodes[j];
+  const uint32_t r0 = orow[a], r1 = orow[a + 1];
+  const int lane = lane_id();
+  for (;;) {
+    uint32_t t = 0;
+    if (lane == 0) t = atomicAdd(&ctl[0], 1u);
+    const uint32_t p = r0 + __builtin_amdgcn_readfirstlane(t);
+    if (p >= r1) break;
+    const uint32_t y = ocol[p];
+    const uint32_t yb = orow[y], ye = orow[y + 1];
+    if (lower <= 1 && lane == 0) vt_mark(bm, y);
+    if (ye == yb) continue;
+    if constexpr (U == 2) {  // y's row is the last level
+      if (ex && y != a) {
+        uint32_t old = 0;
+        if (lane == 0) old = atomicOr(&ex[y >> 5], 1u << (y & 31));
+        if ((__builtin_amdgcn_readfirstlane(old) >> (y & 31)) & 1u) continue;
+      }
+    }
+    vt_walk<1, U>(orow, ocol, bm, ex, lower, yb, ye, p, VT_NONE, VT_NONE, a, y, VT_NONE, VT_NONE, lane);
+  }
+  __syncthreads();
+  uint32_t c = 0;
+  for (uint32_t w = threadIdx.x; w < W; w += VT_BLOCK) c += (uint32_t)__popc(bm[w] & tmask[w]);
+  c = wave_reduce_sum(c);
+  if (lane == 0 && c) atomicAdd(&ctl[1], c);
+  __syncthreads();
+  if (threadIdx.x == 0) reach[j] = (int64_t)ctl[1];
+}
+
 // HBM budget of the three MS-BFS state arrays (sources are batched to fit)
 constexpr double VR_STATE_BUDGET = 24e9;
 
@@ -287,7 +462,78 @@ struct VrIndex {
   uint32_t D = 0;
   int64_t ns = 0;
   BufPtr dict, si, di, tflag, src_nodes, rowptr, cols, order, srcpos;
+  // the trail part (lower bound ≥ 2), built by the first trail query: out-CSR
+  // by source (a rel's identity = its position in ocol), target bitmask of
+  // ⌈D/32⌉ words, sources by decreasing out-degree
+  std::mutex vt_mu;
+  BufPtr orow, ocol, tmask, sorder;
 };
+
+static void vt_build(Session *s, VrIndex &ix, int64_t m) {
+  std::lock_guard<std::mutex> lk(ix.vt_mu);
+  if (ix.orow) return;
+  const uint32_t D = ix.D;
+  const int64_t W = ((int64_t)D + 31) / 32;
+  const unsigned g = grid_for(m, 256, 256 * 64);
+  BufPtr deg = s->alloc(4 * ((int64_t)D + 1)), orow = s->alloc(4 * ((int64_t)D + 1));
+  BufPtr cursor = s->alloc(4 * ((int64_t)D + 1)), ocol = s->alloc(4 * m), tmask = s->alloc(4 * W);
+  BufPtr skey = s->alloc(8 * ix.ns), sorder = s->alloc(8 * ix.ns);
+  HIP_CHECK(hipMemsetAsync(deg->p, 0, 4 * ((int64_t)D + 1), s->stream));
+  {
+    KernelTimer kt(s, "vt_index", 16.0 * m);
+    hipLaunchKernelGGL(k_vr_indeg, dim3(g), dim3(256), 0, s->stream, (const uint32_t *)ix.si->p, m,
+                       (uint32_t *)deg->p);
+    BufPtr tot = s->alloc(16);
+    exclusive_scan_u32_async(s, (const uint32_t *)deg->p, (uint32_t *)orow->p, (int64_t)D + 1,
+                             (uint32_t *)tot->p);
+    HIP_CHECK(hipMemcpyAsync(cursor->p, orow->p, 4 * ((int64_t)D + 1), hipMemcpyDeviceToDevice,
+                             s->stream));
+    // rows keyed by the rel's source, holding its target
+    hipLaunchKernelGGL(k_vr_fill, dim3(g), dim3(256), 0, s->stream, (const uint32_t *)ix.di->p,
+                       (const uint32_t *)ix.si->p, m, (uint32_t *)cursor->p, (uint32_t *)ocol->p);
+    hipLaunchKernelGGL(k_vt_tmask, dim3(grid_for(W, 256)), dim3(256), 0, s->stream,
+                       (const uint8_t *)ix.tflag->p, D, (uint32_t *)tmask->p);
+    hipLaunchKernelGGL(k_vt_srckey, dim3(grid_for(ix.ns, 256)), dim3(256), 0, s->stream,
+                       (const int64_t *)ix.src_nodes->p, ix.ns, (const uint32_t *)orow->p,
+                       (uint64_t *)skey->p);
+    KERNEL_CHECK();
+    vr_rocprim(s, [&](void *t, size_t &n) {
+      return rocprim::radix_sort_keys(t, n, (const uint64_t *)skey->p, (uint64_t *)sorder->p,
+                                      (size_t)ix.ns, 0, 64, s->stream);
+    });
+  }
+  s->sync();  // deg / cursor / skey are released here
+  ix.ocol = ocol;
+  ix.tmask = tmask;
+  ix.sorder = sorder;
+  ix.orow = orow;
+}
+
+// reach[j] of every source j by trail enumeration (lower ≥ 2, upper ≤ 4)
+static void vt_reach(Session *s, VrIndex &ix, int64_t m, int lower, int upper, int64_t *reach) {
+  vt_build(s, ix, m);
+  static bool attr_set = false;
+  const int max_lds = (int)VT_LDS_MAX;
+  if (!attr_set) {
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_vt_trails<2>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_vt_trails<3>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_vt_trails<4>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+    attr_set = true;
+  }
+  const uint32_t D = ix.D;
+  // the expanded-rows bitmap while two bitmaps fit the LDS (D up to about 655 k);
+  // CAPF_VT_EXPAND=0 (tests, tuning): never
+  const size_t wp = (size_t)(((D + 31) / 32 + 3) & ~3u);
+  const char *ve = getenv("CAPF_VT_EXPAND");
+  const int use_ex = !(ve && atoi(ve) == 0) && 4 * (2 * wp + 4) <= VT_LDS_MAX;
+  const size_t lds = 4 * ((use_ex ? 2 * wp : wp) + 4);
+  auto *k = upper == 2 ? k_vt_trails<2> : upper == 3 ? k_vt_trails<3> : k_vt_trails<4>;
+  KernelTimer kt(s, "vt_trails", 4.0 * m);
+  hipLaunchKernelGGL(k, dim3((unsigned)ix.ns), dim3(VT_BLOCK), lds, s->stream, (const uint32_t *)ix.orow->p,
+                     (const uint32_t *)ix.ocol->p, (const uint64_t *)ix.sorder->p,
+                     (const int64_t *)ix.src_nodes->p, (const uint32_t *)ix.tmask->p, D, lower, use_ex, reach);
+  KERNEL_CHECK();
+}
 
 static std::shared_ptr<VrIndex> vr_build(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m,
                                          const ColPtr &sid, int64_t ns_in, const ColPtr &tid, int64_t nt) {
@@ -401,53 +647,15 @@ struct VrCache {
   std::shared_ptr<VrIndex> ix;
 };
 
-DataPtr var_length_reach_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m,
-                                const ColPtr &sid, int64_t ns_in, const ColPtr &tid, int64_t nt,
-                                int upper, bool include_self) {
-  auto out = std::make_shared<Data>();
-  out->cols = {make_column(s, Type::Int64, 0, false), make_column(s, Type::Int64, 0, false)};
-  if (include_self && ns_in > 0 && (m == 0 || nt == 0)) {  // no walks: every (a, a) alone (unique ids: the caller's)
-    ColPtr a = decode_column(s, sid), r = make_column(s, Type::Int64, ns_in, false);
-    hipLaunchKernelGGL(k_vr_ones, dim3(grid_for(ns_in, 256)), dim3(256), 0, s->stream, (int64_t *)r->data->p,
-                       ns_in);
-    KERNEL_CHECK();
-    out->nrows = ns_in;
-    out->cols = {a, r};
-    return out;
-  }
-  if (m == 0 || ns_in == 0 || nt == 0) return out;
-  if (m >= (int64_t(1) << 32)) not_impl("var-length reach: more than 2^32 rels");
-  std::shared_ptr<VrIndex> ix;
-  {
-    std::lock_guard<std::mutex> lk(rsrc->mu);
-    if (rsrc->vr_index) {
-      auto vc = std::static_pointer_cast<VrCache>(rsrc->vr_index);
-      if (vc->rdst.lock() == rdst && vc->sid.lock() == sid && vc->tid.lock() == tid && vc->m == m &&
-          vc->ns_in == ns_in && vc->nt == nt)
-        ix = vc->ix;
-    }
-  }
-  if (!ix) {
-    ix = vr_build(s, rsrc, rdst, m, sid, ns_in, tid, nt);
-    auto vc = std::make_shared<VrCache>();
-    vc->rdst = rdst;
-    vc->sid = sid;
-    vc->tid = tid;
-    vc->m = m;
-    vc->ns_in = ns_in;
-    vc->nt = nt;
-    vc->ix = ix;
-    std::lock_guard<std::mutex> lk(rsrc->mu);
-    rsrc->vr_index = vc;
-  }
+// 4. MS-BFS in batches of 64·K sources: reach[j] of every source j
+static void vr_bfs(Session *s, const VrIndex &ixr, int64_t m, int upper, bool include_self,
+                   const BufPtr &reach) {
+  const VrIndex *ix = &ixr;
   const uint32_t D = ix->D;
   const int64_t ns = ix->ns;
-  const uint64_t *dk = (const uint64_t *)ix->dict->p;
   const BufPtr &si = ix->si, &di = ix->di, &tflag = ix->tflag, &src_nodes = ix->src_nodes;
   const BufPtr &rowptr = ix->rowptr, &cols = ix->cols, &order = ix->order, &srcpos = ix->srcpos;
   const unsigned g = grid_for(m, 256, 256 * 64);
-  // 4. MS-BFS in batches of 64·K sources
-  BufPtr reach = s->alloc(8 * std::max<int64_t>(ns, 1));
   // CAPF_VR_BUDGET (tests): a smaller state budget in bytes → more source batches
   const char *vb = getenv("CAPF_VR_BUDGET");
   const double budget = vb && atof(vb) > 0 ? atof(vb) : (double)VR_STATE_BUDGET;
@@ -505,6 +713,59 @@ DataPtr var_length_reach_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst
       }
     }
   }
+}
+
+DataPtr var_length_reach_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m,
+                                const ColPtr &sid, int64_t ns_in, const ColPtr &tid, int64_t nt,
+                                int lower, int upper) {
+  const bool include_self = lower == 0;
+  auto out = std::make_shared<Data>();
+  out->cols = {make_column(s, Type::Int64, 0, false), make_column(s, Type::Int64, 0, false)};
+  if (include_self && ns_in > 0 && (m == 0 || nt == 0)) {  // no walks: every (a, a) alone (unique ids: the caller's)
+    ColPtr a = decode_column(s, sid), r = make_column(s, Type::Int64, ns_in, false);
+    hipLaunchKernelGGL(k_vr_ones, dim3(grid_for(ns_in, 256)), dim3(256), 0, s->stream, (int64_t *)r->data->p,
+                       ns_in);
+    KERNEL_CHECK();
+    out->nrows = ns_in;
+    out->cols = {a, r};
+    return out;
+  }
+  if (m == 0 || ns_in == 0 || nt == 0) return out;
+  if (m >= (int64_t(1) << 32)) not_impl("var-length reach: more than 2^32 rels");
+  std::shared_ptr<VrIndex> ix;
+  {
+    std::lock_guard<std::mutex> lk(rsrc->mu);
+    if (rsrc->vr_index) {
+      auto vc = std::static_pointer_cast<VrCache>(rsrc->vr_index);
+      if (vc->rdst.lock() == rdst && vc->sid.lock() == sid && vc->tid.lock() == tid && vc->m == m &&
+          vc->ns_in == ns_in && vc->nt == nt)
+        ix = vc->ix;
+    }
+  }
+  if (!ix) {
+    ix = vr_build(s, rsrc, rdst, m, sid, ns_in, tid, nt);
+    auto vc = std::make_shared<VrCache>();
+    vc->rdst = rdst;
+    vc->sid = sid;
+    vc->tid = tid;
+    vc->m = m;
+    vc->ns_in = ns_in;
+    vc->nt = nt;
+    vc->ix = ix;
+    std::lock_guard<std::mutex> lk(rsrc->mu);
+    rsrc->vr_index = vc;
+  }
+  const uint32_t D = ix->D;
+  const int64_t ns = ix->ns;
+  // CAPF_VT_MAX_NODES (tests): a lower node limit of the trail kernel
+  const char *vm = getenv("CAPF_VT_MAX_NODES");
+  const int64_t vt_max = vm && atoll(vm) > 0 ? std::min<int64_t>(atoll(vm), VT_MAX_NODES) : VT_MAX_NODES;
+  if (lower >= 2 && ((int64_t)D > vt_max || m >= (int64_t(1) << 31))) return nullptr;
+  const uint64_t *dk = (const uint64_t *)ix->dict->p;
+  const BufPtr &src_nodes = ix->src_nodes;
+  BufPtr reach = s->alloc(8 * std::max<int64_t>(ns, 1));
+  if (lower >= 2) vt_reach(s, *ix, m, lower, upper, (int64_t *)reach->p);
+  else vr_bfs(s, *ix, m, upper, include_self, reach);
   // 5. rows (a, reach) for the sources that reach at least one target (every
   // source from lower bound 0)
   BufPtr pos = s->alloc(std::max<int64_t>(ns, 1));
@@ -548,7 +809,9 @@ extern "C" capf_status capf_var_length_reach(capf_session *cs, capf_table *rels,
     if (!cs || !rels || !src_col || !dst_col || !sources || !source_id_col || !targets ||
         !target_id_col || !out_source_col || !out_reach_col || !out)
       illegal("null argument");
-    if (lower != 1 && lower != 0) not_impl("var-length reach: only lower bounds 0 and 1 are fused");
+    if (lower < 0) not_impl("var-length reach: negative lower bound");
+    if (lower >= 2 && !(lower <= upper && upper <= 4))
+      not_impl("var-length reach: lower bounds from 2 are fused for 2 <= lower <= upper <= 4 only");
     if (upper < 1 || upper > 64) illegal("var-length reach: upper bound out of range");
     if (!strcmp(out_source_col, out_reach_col)) illegal("output column names must differ");
     Session *s = &cs->impl;
@@ -557,7 +820,8 @@ extern "C" capf_status capf_var_length_reach(capf_session *cs, capf_table *rels,
     ColPtr rs = int_column_of(rels->node, dr, src_col), rd = int_column_of(rels->node, dr, dst_col);
     ColPtr si = int_column_of(sources->node, ds, source_id_col);
     ColPtr ti = int_column_of(targets->node, dt, target_id_col);
-    DataPtr d = var_length_reach_rows(s, rs, rd, dr->nrows, si, ds->nrows, ti, dt->nrows, upper, lower == 0);
+    DataPtr d = var_length_reach_rows(s, rs, rd, dr->nrows, si, ds->nrows, ti, dt->nrows, lower, upper);
+    if (!d) not_impl("var-length reach: more nodes than the trail kernel's LDS bitmap holds (2^20)");
     auto n = std::make_shared<Node>();
     n->s = s;
     n->kind = Kind::Source;

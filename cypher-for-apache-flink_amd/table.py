@@ -224,7 +224,10 @@ class GpuSession:
     def var_length_reach(self, rels, src_col, dst_col, sources, source_id_col, targets, target_id_col,
                          lower, upper, out_source_col, out_reach_col):
         """Fused VarLengthExpand → Distinct(a, b) → Aggregate(a, count(*))
-        (capf_var_length_reach): one row (a, reach) per source reaching a target."""
+        (capf_var_length_reach): one row (a, reach) per source reaching a target.
+        lower 0 / 1: walks (multi-source BFS).  2 <= lower <= upper <= 4: trails
+        (pairwise distinct rels; every row of `rels` is one rel), at most 2^20
+        distinct ids.  Other bounds raise NotImplementedException."""
         h = c_void_p()
         _lib.call("capf_var_length_reach", self._h, rels._h, src_col.encode(), dst_col.encode(), sources._h,
                   source_id_col.encode(), targets._h, target_id_col.encode(), int(lower), int(upper),

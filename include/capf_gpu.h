@@ -265,7 +265,8 @@ capf_status capf_session_profile_count(capf_session *s, int32_t *n);
 capf_status capf_session_profile_entry(capf_session *s, int32_t i, const char **kernel,
                                        int64_t *launches, double *total_ms, double *bytes);
 /* last fused execution path taken ("fused_chain2", "fused_triangle", "message_passing",
- * "fused_var_length_reach"; "none" until one runs) */
+ * "fused_var_length_reach" (lower bound 0 / 1: BFS), "fused_var_length_trails"
+ * (lower bound >= 2: trail enumeration); "none" until one runs) */
 const char *capf_session_last_plan(capf_session *s);
 
 /* String dictionary for CAPF_TYPE_STRING columns. */
@@ -470,8 +471,14 @@ capf_status capf_edge_list_read(capf_session *s, const char *path, const char *s
  * without materialising the paths.  lower = 1 (rel isomorphism cannot change
  * the distinct pairs) and lower = 0 (the copyElement branch,
  * VarLengthExpandPlanner.scala:180-205: every source also pairs with itself,
- * so every source has a row; source ids unique) are fused; other bounds
- * return CAPF_ERR_NOT_IMPLEMENTED and the caller plans the join chain.     */
+ * so every source has a row; source ids unique) run the multi-source BFS.
+ * 2 <= lower <= upper <= 4: from lower bound 2 the distinct pairs are those
+ * joined by a TRAIL (pairwise distinct relationships), which one workgroup
+ * per source enumerates; every row of `rels` is one relationship (parallel
+ * rows are different relationships, a self-loop row is one), and the id
+ * dictionary (rel endpoints, sources, targets) may hold at most 2^20 nodes.
+ * Other bounds with lower >= 2, and a larger dictionary, return
+ * CAPF_ERR_NOT_IMPLEMENTED and the caller plans the join chain.            */
 capf_status capf_var_length_reach(capf_session *s, capf_table *rels, const char *src_col,
                                   const char *dst_col, capf_table *sources,
                                   const char *source_id_col, capf_table *targets,

@@ -153,7 +153,9 @@ object Native {
   @native def edgeListRead(session: Long, path: String, sep: String, comment: String, idCol: String,
                            srcCol: String, dstCol: String): Long
 
-  // fused var-length reach (VarLengthExpandPlanner.scala:82-259 → Distinct → Aggregate)
+  // fused var-length reach (VarLengthExpandPlanner.scala:82-259 → Distinct → Aggregate):
+  // lower 0 / 1 by multi-source BFS; 2 <= lower <= upper <= 4 by trail enumeration (each row
+  // of `rels` one relationship, at most 2^20 distinct ids); other bounds: NotImplemented
   @native def varLengthReach(session: Long, rels: Long, srcCol: String, dstCol: String, sources: Long,
                              sourceId: String, targets: Long, targetId: String, lower: Int, upper: Int,
                              outSource: String, outReach: String): Long
