@@ -598,6 +598,13 @@ bool try_fused_reach(const NodePtr &grp, DataPtr &out);
 DataPtr var_length_reach_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m,
                               const ColPtr &sid, int64_t ns_in, const ColPtr &tid, int64_t nt, int lower,
                               int upper);
+// The undirected lowering's reach (VarLengthExpandPlanner.scala:277-307), by
+// per-source enumeration of its (node, mode) steps, 0 ≤ lower ≤ upper ≤ 4:
+// same dictionary, index cache and output rows; nullptr outside those bounds
+// and above the same node limit.
+DataPtr var_length_reach_undirected_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m,
+                                         const ColPtr &sid, int64_t ns_in, const ColPtr &tid, int64_t nt,
+                                         int lower, int upper);
 // Radix-partitioned LDS histograms of the 2-hop count (chain2_partitioned.hip).
 // cols = {start(r1), end(r1), start(r2), end(r2)}, all plain or all FOR32.
 // Histograms hold chain2_hist_len(hi − lo + 1) counters indexed by

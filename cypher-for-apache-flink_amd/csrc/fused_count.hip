@@ -1732,8 +1732,12 @@ static bool leaf_eq(const Leaf &a, const Leaf &b) {
 }
 
 // The chain S_a ⋈ E ⋈ … ⋈ E ⋈ S_b of one branch; `a_cols` are tracked columns
-// that must lie on S_a (the group keys).
-static bool reach_branch(const ReachBranch &br, const std::vector<int> &a_cols, ReachShape &sh) {
+// that must lie on S_a (the group keys).  With `links` (the undirected
+// lowering) every rel leaf may be entered and left by either endpoint column,
+// or by one column twice: the (entry, exit) column pairs are recorded for the
+// caller to judge, and sh.cs / sh.cd stay unset.
+static bool reach_branch(const ReachBranch &br, const std::vector<int> &a_cols, ReachShape &sh,
+                         std::vector<std::pair<int, int>> *links = nullptr) {
   JoinGraph g;
   std::vector<ColRef> refs;
   if (br.base->kind != Kind::Join && br.base->kind != Kind::Filter) return reach_reject("branch check 1");
@@ -1790,11 +1794,15 @@ static bool reach_branch(const ReachBranch &br, const std::vector<int> &a_cols, 
     const Leaf &lr = g.leaves[cur];
     if (sh.k == 0) sh.rel = lr;
     else if (!leaf_eq(lr, sh.rel)) return reach_reject("branch check 10");
-    if (entry != sh.cs) return reach_reject("branch check 11");
+    if (!links && entry != sh.cs) return reach_reject("branch check 11");
     const auto &out = e[0].second.leaf == prev && e[0].first == entry ? e[1] : e[0];
-    if (out.first == entry) return reach_reject("branch check 12");
-    if (sh.k == 0) sh.cd = out.first;
-    else if (out.first != sh.cd) return reach_reject("branch check 13");
+    if (links) {
+      links->emplace_back(entry, out.first);
+    } else {
+      if (out.first == entry) return reach_reject("branch check 12");
+      if (sh.k == 0) sh.cd = out.first;
+      else if (out.first != sh.cd) return reach_reject("branch check 13");
+    }
     pos[cur] = sh.k;
     ++sh.k;
     prev = cur;
@@ -1852,6 +1860,226 @@ static bool reach_branch(const ReachBranch &br, const std::vector<int> &a_cols, 
   return true;
 }
 
+// The directed lowering: one chain per length l..u, all on the same leaves and
+// columns.
+static bool directed_shapes(const std::vector<ReachBranch> &brs, const std::vector<int> &a_cols, size_t ntracked,
+                            bool zero, std::vector<ReachShape> &shapes, int &lower_out, int &upper_out) {
+  shapes.assign(brs.size(), ReachShape{});
+  uint64_t lengths = 0;
+  for (size_t b = 0; b < brs.size(); ++b) {
+    if (!reach_branch(brs[b], a_cols, shapes[b])) return reach_reject("a branch is not a var-length chain");
+    const ReachShape &sh = shapes[b], &s0 = shapes[0];
+    if (sh.k > 64 || (lengths >> (sh.k - 1) & 1)) return reach_reject("branch lengths");
+    lengths |= uint64_t(1) << (sh.k - 1);
+    if (!leaf_eq(sh.sa, s0.sa) || !leaf_eq(sh.sb, s0.sb) || !leaf_eq(sh.rel, s0.rel))
+      return reach_reject("branches scan different tables");
+    if (sh.x != s0.x || sh.y != s0.y || sh.cs != s0.cs || sh.cd != s0.cd)
+      return reach_reject("branches join different columns");
+    for (size_t i = 0; i < ntracked; ++i) {
+      const RCol &r = sh.roles[i], &r0 = s0.roles[i];
+      if (r.role != r0.role || r.col != r0.col) return reach_reject("column roles differ across branches");
+      if (r.role == 2 && !prog_eq(r.lit, r0.lit)) return reach_reject("literals differ across branches");
+    }
+  }
+  const int upper = 64 - __builtin_clzll(lengths), lower = __builtin_ctzll(lengths) + 1;
+  if ((lengths >> (lower - 1)) != (upper - lower == 63 ? ~uint64_t(0) : (uint64_t(1) << (upper - lower + 1)) - 1))
+    return reach_reject("lengths are not l..u");
+  if (lower >= 2) {  // trails (var_length_reach.hip::k_vt_trails)
+    if (zero) return reach_reject("a zero-length branch beside lengths from 2");
+    if (upper > 4) return reach_reject("trail lengths above 4");
+    for (auto &sh : shapes)
+      if (!sh.all_neq) return reach_reject("a branch lacks some NOT(e_i = e_j) filters: not a trail");
+  }
+  lower_out = lower;
+  upper_out = upper;
+  return true;
+}
+
+// ---- the undirected lowering (VarLengthExpandPlanner.scala:277-307)
+// Each step joins the (out, in) tables of the step before four ways and
+// unions them pairwise, so its DAG has Union nodes BELOW joins.  hoist_unions
+// rewrites a node into union-free alternatives whose UNION ALL it is: a Union
+// over joins contributes the alternatives of both inputs (the second one's
+// columns realigned by name, as union_branches does), and Join / Filter /
+// Select / literal-only WithColumns above it are copied once per combination
+// of their inputs' alternatives.  The copies are temporary plan nodes (as
+// filter_node builds them) that only `collect` reads; leaves are never copied,
+// so leaf identity holds across alternatives.  A Union with no join beneath (a
+// node scan over several label tables) stays the opaque leaf it is to `collect`.
+constexpr size_t HOIST_MAX = 64;  // alternatives of one node
+
+struct Hoist {
+  std::map<const Node *, std::vector<NodePtr>> memo;
+  std::map<const Node *, bool> joins;
+  bool failed = false;
+};
+
+static bool is_materialised(const NodePtr &n) {
+  std::lock_guard<std::mutex> lk(n->mu);
+  return n->result != nullptr;
+}
+
+static bool has_join(const NodePtr &n, Hoist &h) {
+  auto it = h.joins.find(n.get());
+  if (it != h.joins.end()) return it->second;
+  bool j = false;
+  if (!is_materialised(n)) {
+    j = n->kind == Kind::Join;
+    for (auto &k : n->kids) j = j || has_join(k, h);
+  }
+  h.joins[n.get()] = j;
+  return j;
+}
+
+static NodePtr with_kids(const NodePtr &n, std::vector<NodePtr> kids) {
+  auto c = std::make_shared<Node>();
+  c->s = n->s;
+  c->kind = n->kind;
+  c->names = n->names;
+  c->types = n->types;
+  c->kids = std::move(kids);
+  c->sel_index = n->sel_index;
+  c->pred = n->pred;
+  c->join_type = n->join_type;
+  c->join_keys = n->join_keys;
+  c->exprs = n->exprs;
+  c->target_index = n->target_index;
+  return c;
+}
+
+static std::vector<NodePtr> hoist_unions(const NodePtr &n, Hoist &h) {
+  if (h.failed) return {};
+  auto it = h.memo.find(n.get());
+  if (it != h.memo.end()) return it->second;
+  std::vector<NodePtr> out;
+  bool through = false;  // an operator `collect` looks through
+  if (!is_materialised(n)) {
+    switch (n->kind) {
+      case Kind::Select:
+      case Kind::Filter: through = true; break;
+      case Kind::Join: through = n->join_type == CAPF_JOIN_INNER; break;
+      case Kind::WithColumns:
+        through = true;
+        for (auto &p : n->exprs) through = through && is_literal_program(p);
+        break;
+      default: break;
+    }
+  }
+  if (!is_materialised(n) && n->kind == Kind::Union && n->kids.size() == 2 && has_join(n, h)) {
+    out = hoist_unions(n->kids[0], h);
+    std::vector<int> idx;
+    for (auto &nm : n->names) {
+      idx.push_back(n->kids[1]->col_index(nm));
+      if (idx.back() < 0) h.failed = true;
+    }
+    for (auto &r : hoist_unions(n->kids[1], h)) {
+      auto sel = std::make_shared<Node>();
+      sel->s = n->s;
+      sel->kind = Kind::Select;
+      sel->names = n->names;
+      sel->types = n->types;
+      sel->kids = {r};
+      sel->sel_index = idx;
+      out.push_back(sel);
+    }
+  } else if (through && n->kids.size() == 1) {
+    for (auto &k : hoist_unions(n->kids[0], h)) out.push_back(k == n->kids[0] ? n : with_kids(n, {k}));
+  } else if (through && n->kids.size() == 2) {
+    const std::vector<NodePtr> l = hoist_unions(n->kids[0], h), r = hoist_unions(n->kids[1], h);
+    if (l.size() * r.size() > HOIST_MAX) h.failed = true;
+    else
+      for (auto &a : l)
+        for (auto &b : r) out.push_back(a == n->kids[0] && b == n->kids[1] ? n : with_kids(n, {a, b}));
+  } else {
+    out = {n};
+  }
+  if (out.size() > HOIST_MAX) h.failed = true;
+  if (h.failed) return {};
+  h.memo[n.get()] = out;
+  return out;
+}
+
+// Every hoisted alternative of length k must be one mode vector m ∈ {out, in}^k
+// of the automaton (var_length_reach.hip, "undirected steps"), link by link,
+// with cs / cd the rel's start / end column:
+//   S_a.id = e_1.(m_1 = out ? cs : cd)
+//   e_i leaves by (m_i = out ? cd : cs); e_{i+1} is entered by cs when
+//   m_i = m_{i+1} and by cd otherwise; the last exit joins S_b.id
+// and the alternatives must be all 2^k vectors of every length l..u ≤ 4, each
+// with all its NOT(e_i = e_j) filters, on the same three leaves and columns.
+// Which of the two columns is the start follows from the links (the two
+// readings agree only where no alternative has a link, u = 1, and there they
+// give the same pairs).
+static bool undirected_shapes(const std::vector<ReachBranch> &brs, const std::vector<int> &a_cols, size_t ntracked,
+                              bool zero, std::vector<ReachShape> &shapes, int &lower_out, int &upper_out) {
+  Hoist hz;
+  std::vector<ReachBranch> hb;
+  for (auto &br : brs) {
+    for (auto &alt : hoist_unions(br.base, hz)) hb.push_back(ReachBranch{alt, br.cols});
+    if (hz.failed || hb.size() > HOIST_MAX) return reach_reject("undirected: too many union alternatives");
+  }
+  if (hb.empty()) return reach_reject("undirected: no alternatives");
+  shapes.assign(hb.size(), ReachShape{});
+  std::vector<std::vector<std::pair<int, int>>> links(hb.size());
+  int c0 = -1, c1 = -1;  // the two rel columns the links use
+  for (size_t b = 0; b < hb.size(); ++b) {
+    if (!reach_branch(hb[b], a_cols, shapes[b], &links[b])) return reach_reject("undirected: an alternative is not a chain");
+    const ReachShape &sh = shapes[b], &s0 = shapes[0];
+    if (sh.k > 4) return reach_reject("undirected lengths above 4");
+    if (!sh.all_neq) return reach_reject("undirected: an alternative lacks some NOT(e_i = e_j) filters");
+    if (!leaf_eq(sh.sa, s0.sa) || !leaf_eq(sh.sb, s0.sb) || !leaf_eq(sh.rel, s0.rel))
+      return reach_reject("undirected: alternatives scan different tables");
+    if (sh.x != s0.x || sh.y != s0.y) return reach_reject("undirected: alternatives join different id columns");
+    for (size_t i = 0; i < ntracked; ++i) {
+      const RCol &r = sh.roles[i], &r0 = s0.roles[i];
+      if (r.role != r0.role || r.col != r0.col) return reach_reject("undirected: column roles differ");
+      if (r.role == 2 && !prog_eq(r.lit, r0.lit)) return reach_reject("undirected: literals differ");
+    }
+    for (auto &lk : links[b])
+      for (int c : {lk.first, lk.second}) {
+        if (c == c0 || c == c1) continue;
+        if (c0 < 0) c0 = c;
+        else if (c1 < 0) c1 = c;
+        else return reach_reject("undirected: more than two rel columns joined");
+      }
+  }
+  if (c1 < 0) return reach_reject("undirected: one rel column joined");
+  for (int turn = 0; turn < 2; ++turn) {
+    const int cs = turn ? c1 : c0, cd = turn ? c0 : c1;
+    uint32_t seen[5] = {0, 0, 0, 0, 0};  // per length: the mode vectors met (bit = vector, in = 1)
+    bool ok = true;
+    for (size_t b = 0; b < hb.size() && ok; ++b) {
+      const auto &lk = links[b];
+      uint32_t vec = 0;
+      for (size_t i = 0; i < lk.size() && ok; ++i) {
+        const bool in = lk[i].second == cs;
+        const bool same = i == 0 ? !in : in == (bool)((vec >> (i - 1)) & 1u);  // the start state is (a, out)
+        ok = lk[i].first == (same ? cs : cd);
+        vec |= (in ? 1u : 0u) << i;
+      }
+      seen[lk.size()] |= 1u << vec;
+    }
+    int lower = 0, upper = 0;
+    for (int k = 1; k <= 4 && ok; ++k) {
+      if (!seen[k]) continue;
+      ok = seen[k] == (k == 4 ? 0xFFFFu : (1u << (1u << k)) - 1u);  // all 2^k vectors
+      if (!lower) lower = k;
+      else if (upper != k - 1) ok = false;  // contiguous
+      upper = k;
+    }
+    if (!ok) continue;
+    if (zero && lower >= 2) return reach_reject("a zero-length branch beside lengths from 2");
+    for (auto &sh : shapes) {
+      sh.cs = cs;
+      sh.cd = cd;
+    }
+    lower_out = lower;
+    upper_out = upper;
+    return true;
+  }
+  return reach_reject("undirected: the alternatives are not all mode vectors of lengths l..u");
+}
+
 bool try_fused_reach(const NodePtr &grp, DataPtr &result) {
   const char *fe = getenv("CAPF_FUSED_REACH");  // 0: always the relational plan
   if (fe && atoi(fe) == 0) return false;
@@ -1899,31 +2127,12 @@ bool try_fused_reach(const NodePtr &grp, DataPtr &result) {
   const ReachBranch zbr = zero >= 0 ? brs[(size_t)zero] : ReachBranch{};
   if (zero >= 0) brs.erase(brs.begin() + zero);
   if (brs.empty()) return reach_reject("no var-length chain");
-  std::vector<ReachShape> shapes(brs.size());
-  uint64_t lengths = 0;
-  for (size_t b = 0; b < brs.size(); ++b) {
-    if (!reach_branch(brs[b], a_cols, shapes[b])) return reach_reject("a branch is not a var-length chain");
-    const ReachShape &sh = shapes[b], &s0 = shapes[0];
-    if (sh.k > 64 || (lengths >> (sh.k - 1) & 1)) return reach_reject("branch lengths");
-    lengths |= uint64_t(1) << (sh.k - 1);
-    if (!leaf_eq(sh.sa, s0.sa) || !leaf_eq(sh.sb, s0.sb) || !leaf_eq(sh.rel, s0.rel))
-      return reach_reject("branches scan different tables");
-    if (sh.x != s0.x || sh.y != s0.y || sh.cs != s0.cs || sh.cd != s0.cd)
-      return reach_reject("branches join different columns");
-    for (size_t i = 0; i < tracked.size(); ++i) {
-      const RCol &r = sh.roles[i], &r0 = s0.roles[i];
-      if (r.role != r0.role || r.col != r0.col) return reach_reject("column roles differ across branches");
-      if (r.role == 2 && !prog_eq(r.lit, r0.lit)) return reach_reject("literals differ across branches");
-    }
-  }
-  const int upper = 64 - __builtin_clzll(lengths), lower = __builtin_ctzll(lengths) + 1;
-  if ((lengths >> (lower - 1)) != (upper - lower == 63 ? ~uint64_t(0) : (uint64_t(1) << (upper - lower + 1)) - 1))
-    return reach_reject("lengths are not l..u");
-  if (lower >= 2) {  // trails (var_length_reach.hip::k_vt_trails)
-    if (zero >= 0) return reach_reject("a zero-length branch beside lengths from 2");
-    if (upper > 4) return reach_reject("trail lengths above 4");
-    for (auto &sh : shapes)
-      if (!sh.all_neq) return reach_reject("a branch lacks some NOT(e_i = e_j) filters: not a trail");
+  std::vector<ReachShape> shapes;
+  int lower = 0, upper = 0;
+  bool undirected = false;
+  if (!directed_shapes(brs, a_cols, tracked.size(), zero >= 0, shapes, lower, upper)) {
+    if (!undirected_shapes(brs, a_cols, tracked.size(), zero >= 0, shapes, lower, upper)) return false;
+    undirected = true;
   }
   const ReachShape &sh = shapes[0];
   // DISTINCT over (a, b): both ids among its keys, every key a column of S_a /
@@ -1975,10 +2184,11 @@ bool try_fused_reach(const NodePtr &grp, DataPtr &result) {
     if ((*c)->type != Type::Int64 || (*c)->valid) return reach_reject("nullable or non-INTEGER ids");
   }
   if (lr.data->nrows >= (int64_t(1) << 32)) return reach_reject("more than 2^32 rels");
-  DataPtr res = var_length_reach_rows(s, rs, rd, lr.data->nrows, xa, la.data->nrows, yb,
-                                      lb.data->nrows, zero >= 0 ? 0 : lower, upper);
-  if (!res) return reach_reject("more nodes than the trail kernel's LDS bitmap holds");
-  s->last_plan = lower >= 2 ? "fused_var_length_trails" : "fused_var_length_reach";
+  const auto rows = undirected ? var_length_reach_undirected_rows : var_length_reach_rows;
+  DataPtr res = rows(s, rs, rd, lr.data->nrows, xa, la.data->nrows, yb, lb.data->nrows, zero >= 0 ? 0 : lower, upper);
+  if (!res) return reach_reject("more nodes than the enumeration kernel's LDS bitmap holds");
+  s->last_plan = undirected ? "fused_var_length_undirected"
+                 : lower >= 2 ? "fused_var_length_trails" : "fused_var_length_reach";
   // output: group keys (a's id, other S_a columns gathered by a's row, literals)
   // then one reach column per count(*)
   const int64_t nr = res->nrows;

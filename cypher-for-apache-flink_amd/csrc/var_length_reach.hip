@@ -30,7 +30,9 @@
 // within a fixed HBM budget.  Bytes per level ≈ 8·K·(M + 3·D).
 //
 // Lower bound ≥ 2 (≤ upper ≤ 4) is answered by trail enumeration instead:
-// k_vt_trails below ("trails").
+// k_vt_trails below ("trails"); the undirected pattern (0 ≤ lower ≤ upper ≤ 4)
+// by enumeration of its lowering's (node, mode) steps: k_vu_steps ("undirected
+// steps").
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -449,6 +451,218 @@ __global__ __launch_bounds__(VT_BLOCK) void k_vt_trails(const uint32_t *__restri
   if (threadIdx.x == 0) reach[j] = (int64_t)ctl[1];
 }
 
+// ------------------------------------------------------------------ undirected steps
+// The undirected lowering (VarLengthExpandPlanner.scala:277-307) is an automaton
+// over states (node x, mode out | in), from (a, out): a rel e not yet on the
+// path leads
+//   (x, out), start(e) = x → (end(e), out)      (x, in), start(e) = x → (x, in)
+//   (x, out), end(e) = x → (start(e), in)       (x, in), end(e) = x → (x, out)
+// (after an inbound step the next step does not move), and a state of depth
+// max(lower, 1)..upper pairs a with its node.  One workgroup per source
+// enumerates these steps as k_vt_trails enumerates trails; a rel's identity
+// is its position in the out-CSR, which every in-CSR entry carries beside the
+// other endpoint (iadj: x = start node, y = out position), so the rels of a
+// path compare as out positions whichever row they were taken from.  A state's
+// two rows are walked as one range: [0, od) the out-row, [od, tot) the in-row.
+constexpr uint32_t VU_OUT = 0, VU_IN = 1;
+
+struct VuCsr {
+  const uint32_t *__restrict__ orow, *__restrict__ ocol, *__restrict__ irow;
+  const uint2 *__restrict__ iadj;
+};
+
+// records where each rel row lands in the out-CSR (k_vr_fill does not)
+__global__ void k_vu_fill_out(const uint32_t *si, const uint32_t *di, int64_t m, uint32_t *cursor,
+                              uint32_t *ocol, uint32_t *opos) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t p = atomicAdd(&cursor[si[i]], 1u);
+    ocol[p] = di[i];
+    opos[i] = p;
+  }
+}
+
+__global__ void k_vu_fill_in(const uint32_t *si, const uint32_t *di, const uint32_t *opos, int64_t m,
+                             uint32_t *cursor, uint2 *iadj) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m;
+       i += (int64_t)gridDim.x * blockDim.x)
+    iadj[atomicAdd(&cursor[di[i]], 1u)] = make_uint2(si[i], opos[i]);
+}
+
+// sources by decreasing total degree (out + in ≤ 2m < 2^32)
+__global__ void k_vu_srckey(const int64_t *src_nodes, int64_t ns, const uint32_t *orow, const uint32_t *irow,
+                            uint64_t *key) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < ns;
+       j += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t a = src_nodes[j];
+    const uint32_t deg = (orow[a + 1] - orow[a]) + (irow[a + 1] - irow[a]);
+    key[j] = ((uint64_t)(0xFFFFFFFFu - deg) << 32) | (uint64_t)j;
+  }
+}
+
+__device__ inline bool vu_free(uint32_t r, uint32_t s1, uint32_t s2, uint32_t s3) {
+  return r != s1 && r != s2 && r != s3;
+}
+
+// The last level from (x, in): every remaining rel leads back to x, so x is an
+// end node iff one of x's row entries is not on the stack.  A stack rel takes
+// one entry off the out-row when its position lies there and one off the
+// in-row when it ends at x (a self-loop on the stack: both).
+__device__ inline bool vu_in_last(const VuCsr &g, uint32_t x, uint32_t s1, uint32_t s2, uint32_t s3) {
+  const uint32_t ob = g.orow[x], oe = g.orow[x + 1];
+  uint32_t left = (oe - ob) + (g.irow[x + 1] - g.irow[x]);
+  if (s1 != VT_NONE) left -= (uint32_t)(s1 >= ob && s1 < oe) + (uint32_t)(g.ocol[s1] == x);
+  if (s2 != VT_NONE) left -= (uint32_t)(s2 >= ob && s2 < oe) + (uint32_t)(g.ocol[s2] == x);
+  if (s3 != VT_NONE) left -= (uint32_t)(s3 >= ob && s3 < oe) + (uint32_t)(g.ocol[s3] == x);
+  return left > 0;
+}
+
+// The wave stands at state (x, mode) after S rels at out positions s1..s3
+// (VT_NONE beyond S); everything but `lane` is wave-uniform.  Last level
+// (S + 1 = U): from mode in the degree test above, from mode out the lanes
+// stride over both rows, skip the stack and mark the other endpoints.  Before
+// it: each lane takes one entry, marks the next state's node when the path is
+// long enough, and the wave descends into the lanes' states one after the
+// other (handed out by readlane).  One level above the last, the lanes settle
+// their own mode-in states by the degree test instead of a descent.
+template <int S, int U>
+__device__ inline void vu_walk(const VuCsr &g, uint32_t *bm, int lower, uint32_t x, uint32_t mode,
+                               uint32_t s1, uint32_t s2, uint32_t s3, int lane) {
+  const uint32_t ob = g.orow[x], od = g.orow[x + 1] - ob;
+  const uint32_t ib = g.irow[x], tot = od + (g.irow[x + 1] - ib);
+  if constexpr (S + 1 >= U) {
+    if (mode == VU_IN) {
+      if (vu_in_last(g, x, s1, s2, s3)) vt_mark(bm, x);  // wave-uniform: see k_vu_steps
+    }
+    // VT_ILP loads in flight per lane; a wave-uniform trip count
+    for (uint32_t t0 = 0; mode == VU_OUT && t0 < tot; t0 += VT_ILP * WAVE) {
+      uint32_t v[VT_ILP];
+      bool on[VT_ILP];
+#pragma unroll
+      for (int i = 0; i < VT_ILP; ++i) {
+        const uint32_t t = t0 + lane + i * WAVE;
+        on[i] = false;
+        v[i] = 0u;
+        if (t < od) {
+          on[i] = vu_free(ob + t, s1, s2, s3);
+          v[i] = g.ocol[ob + t];
+        } else if (t < tot) {
+          const uint2 e = g.iadj[ib + (t - od)];
+          on[i] = vu_free(e.y, s1, s2, s3);
+          v[i] = e.x;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < VT_ILP; ++i)
+        if (on[i]) vt_mark(bm, v[i]);
+    }
+  } else {
+    for (uint32_t t0 = 0; t0 < tot; t0 += WAVE) {
+      const uint32_t t = t0 + lane;
+      uint32_t r = VT_NONE, oth = 0, isin = 0;
+      if (t < od) {
+        r = ob + t;
+        oth = g.ocol[r];
+      } else if (t < tot) {
+        const uint2 e = g.iadj[ib + (t - od)];
+        oth = e.x;
+        r = e.y;
+        isin = 1;
+      }
+      bool ok = t < tot && vu_free(r, s1, s2, s3);
+      const uint32_t ny = mode == VU_IN ? x : oth, nm = mode ^ isin;
+      if (S + 1 >= lower) {
+        if (mode == VU_IN) {  // every lane's next state sits on x
+          if (__ballot(ok)) vt_mark(bm, x);
+        } else if (ok) {
+          vt_mark(bm, ny);
+        }
+      }
+      if constexpr (S + 2 == U) {
+        const bool mine = ok && nm == VU_IN;
+        const bool hit = mine && (S == 1 ? vu_in_last(g, ny, s1, r, VT_NONE) : vu_in_last(g, ny, s1, s2, r));
+        if (mode == VU_IN) {
+          if (__ballot(hit)) vt_mark(bm, x);
+        } else if (hit) {
+          vt_mark(bm, ny);
+        }
+        if (mine) ok = false;
+      }
+      unsigned long long todo = __ballot(ok);
+      while (todo) {
+        const int i = __builtin_amdgcn_readfirstlane(__ffsll(todo) - 1);
+        todo &= todo - 1;
+        const uint32_t qy = __builtin_amdgcn_readlane(ny, i), qm = __builtin_amdgcn_readlane(nm, i);
+        const uint32_t qr = __builtin_amdgcn_readlane(r, i);
+        if constexpr (S == 1) vu_walk<2, U>(g, bm, lower, qy, qm, s1, qr, VT_NONE, lane);
+        else vu_walk<3, U>(g, bm, lower, qy, qm, s1, s2, qr, lane);
+      }
+    }
+  }
+}
+
+// Block blockIdx.x = the source sorder[blockIdx.x], as in k_vt_trails.  Dynamic
+// LDS: the bitmap (⌈D/32⌉ words, padded to 16 B), then the first-hop cursor and
+// the count.  The first hops are a's out-row (to (end, out)) and in-row (to
+// (start, in)); the waves take them from the cursor.
+// No statement of the cursor loop, or of vu_walk's wave-uniform parts, is
+// guarded by `lane == 0`: every lane issues the cursor's atomicAdd (lane 0
+// adds 1, the others 0) and the marks of a wave-uniform node (the same bit;
+// the compiler folds either into one LDS atomic per wave).  With `if (lane ==
+// 0)` guards the compiler threaded the lanes that skip one guard past the
+// next one, across the loop's back edge: those lanes then read the cursor as
+// the constant 0 under a partial exec mask and never left the loop when the
+// source's first hop was an inbound one (an empty out-row).
+template <int U>
+__global__ __launch_bounds__(VT_BLOCK) void k_vu_steps(const uint32_t *__restrict__ orow,
+                                                       const uint32_t *__restrict__ ocol,
+                                                       const uint32_t *__restrict__ irow,
+                                                       const uint2 *__restrict__ iadj,
+                                                       const uint64_t *__restrict__ sorder,
+                                                       const int64_t *__restrict__ src_nodes,
+                                                       const uint32_t *__restrict__ tmask, uint32_t D,
+                                                       int lower, int64_t *reach) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t vu_lds[];
+  const uint32_t W = (D + 31) / 32, Wp = (W + 3) & ~3u;
+  uint32_t *bm = vu_lds, *ctl = vu_lds + Wp;
+  for (uint32_t w = threadIdx.x; w < Wp; w += VT_BLOCK) bm[w] = 0;
+  if (threadIdx.x < 2) ctl[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t j = (int64_t)(uint32_t)sorder[blockIdx.x];
+  const uint32_t a = (uint32_t)src_nodes[j];
+  const int lane = lane_id();
+  if (lower == 0 && threadIdx.x == 0) vt_mark(bm, a);  // the zero-length path
+  if constexpr (U >= 1) {
+    const VuCsr g{orow, ocol, irow, iadj};
+    const uint32_t ob = orow[a], od = orow[a + 1] - ob;
+    const uint32_t ib = irow[a], tot = od + (irow[a + 1] - ib);
+    for (;;) {
+      const uint32_t t = __builtin_amdgcn_readfirstlane(atomicAdd(&ctl[0], lane == 0 ? 1u : 0u));
+      if (t >= tot) break;
+      uint32_t r, y, nm;
+      if (t < od) {
+        r = ob + t;
+        y = ocol[r];
+        nm = VU_OUT;
+      } else {
+        const uint2 e = iadj[ib + (t - od)];
+        y = e.x;
+        r = e.y;
+        nm = VU_IN;
+      }
+      if (lower <= 1) vt_mark(bm, y);
+      if constexpr (U >= 2) vu_walk<1, U>(g, bm, lower, y, nm, r, VT_NONE, VT_NONE, lane);
+    }
+  }
+  __syncthreads();
+  uint32_t c = 0;
+  for (uint32_t w = threadIdx.x; w < W; w += VT_BLOCK) c += (uint32_t)__popc(bm[w] & tmask[w]);
+  c = wave_reduce_sum(c);
+  if (lane == 0 && c) atomicAdd(&ctl[1], c);
+  __syncthreads();
+  if (threadIdx.x == 0) reach[j] = (int64_t)ctl[1];
+}
+
 // HBM budget of the three MS-BFS state arrays (sources are batched to fit)
 constexpr double VR_STATE_BUDGET = 24e9;
 
@@ -467,6 +681,12 @@ struct VrIndex {
   // ⌈D/32⌉ words, sources by decreasing out-degree
   std::mutex vt_mu;
   BufPtr orow, ocol, tmask, sorder;
+  // the undirected part, built by the first undirected query on top of the
+  // trail part (orow, tmask) and the in-CSR's rowptr: an out-CSR filled with
+  // every rel row's position recorded, in-CSR entries (start node, out
+  // position) in rowptr's rows, sources by decreasing out + in degree
+  std::mutex vu_mu;
+  BufPtr uocol, uiadj, usorder;
 };
 
 static void vt_build(Session *s, VrIndex &ix, int64_t m) {
@@ -532,6 +752,60 @@ static void vt_reach(Session *s, VrIndex &ix, int64_t m, int lower, int upper, i
   hipLaunchKernelGGL(k, dim3((unsigned)ix.ns), dim3(VT_BLOCK), lds, s->stream, (const uint32_t *)ix.orow->p,
                      (const uint32_t *)ix.ocol->p, (const uint64_t *)ix.sorder->p,
                      (const int64_t *)ix.src_nodes->p, (const uint32_t *)ix.tmask->p, D, lower, use_ex, reach);
+  KERNEL_CHECK();
+}
+
+static void vu_build(Session *s, VrIndex &ix, int64_t m) {
+  vt_build(s, ix, m);
+  std::lock_guard<std::mutex> lk(ix.vu_mu);
+  if (ix.uocol) return;
+  const uint32_t D = ix.D;
+  const unsigned g = grid_for(m, 256, 256 * 64);
+  BufPtr cursor = s->alloc(4 * ((int64_t)D + 1)), uocol = s->alloc(4 * m), opos = s->alloc(4 * m);
+  BufPtr uiadj = s->alloc(8 * m), skey = s->alloc(8 * ix.ns), usorder = s->alloc(8 * ix.ns);
+  {
+    KernelTimer kt(s, "vu_index", 40.0 * m);
+    HIP_CHECK(hipMemcpyAsync(cursor->p, ix.orow->p, 4 * ((int64_t)D + 1), hipMemcpyDeviceToDevice, s->stream));
+    hipLaunchKernelGGL(k_vu_fill_out, dim3(g), dim3(256), 0, s->stream, (const uint32_t *)ix.si->p,
+                       (const uint32_t *)ix.di->p, m, (uint32_t *)cursor->p, (uint32_t *)uocol->p,
+                       (uint32_t *)opos->p);
+    HIP_CHECK(hipMemcpyAsync(cursor->p, ix.rowptr->p, 4 * ((int64_t)D + 1), hipMemcpyDeviceToDevice, s->stream));
+    hipLaunchKernelGGL(k_vu_fill_in, dim3(g), dim3(256), 0, s->stream, (const uint32_t *)ix.si->p,
+                       (const uint32_t *)ix.di->p, (const uint32_t *)opos->p, m, (uint32_t *)cursor->p,
+                       (uint2 *)uiadj->p);
+    hipLaunchKernelGGL(k_vu_srckey, dim3(grid_for(ix.ns, 256)), dim3(256), 0, s->stream,
+                       (const int64_t *)ix.src_nodes->p, ix.ns, (const uint32_t *)ix.orow->p,
+                       (const uint32_t *)ix.rowptr->p, (uint64_t *)skey->p);
+    KERNEL_CHECK();
+    vr_rocprim(s, [&](void *t, size_t &n) {
+      return rocprim::radix_sort_keys(t, n, (const uint64_t *)skey->p, (uint64_t *)usorder->p,
+                                      (size_t)ix.ns, 0, 64, s->stream);
+    });
+  }
+  s->sync();  // cursor / opos / skey are released here
+  ix.uiadj = uiadj;
+  ix.usorder = usorder;
+  ix.uocol = uocol;
+}
+
+// reach[j] of every source j by step enumeration (undirected, 0 ≤ lower ≤ upper ≤ 4)
+static void vu_reach(Session *s, VrIndex &ix, int64_t m, int lower, int upper, int64_t *reach) {
+  vu_build(s, ix, m);
+  using Kern = void (*)(const uint32_t *, const uint32_t *, const uint32_t *, const uint2 *, const uint64_t *,
+                        const int64_t *, const uint32_t *, uint32_t, int, int64_t *);
+  static const Kern kerns[5] = {k_vu_steps<0>, k_vu_steps<1>, k_vu_steps<2>, k_vu_steps<3>, k_vu_steps<4>};
+  static std::once_flag attr_once;
+  std::call_once(attr_once, [] {
+    for (Kern k : kerns)
+      HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)VT_LDS_MAX));
+  });
+  const uint32_t D = ix.D;
+  const size_t lds = 4 * ((size_t)(((D + 31) / 32 + 3) & ~3u) + 4);
+  KernelTimer kt(s, "vu_steps", 12.0 * m);
+  hipLaunchKernelGGL(kerns[upper], dim3((unsigned)ix.ns), dim3(VT_BLOCK), lds, s->stream,
+                     (const uint32_t *)ix.orow->p, (const uint32_t *)ix.uocol->p, (const uint32_t *)ix.rowptr->p,
+                     (const uint2 *)ix.uiadj->p, (const uint64_t *)ix.usorder->p, (const int64_t *)ix.src_nodes->p,
+                     (const uint32_t *)ix.tmask->p, D, lower, reach);
   KERNEL_CHECK();
 }
 
@@ -715,9 +989,8 @@ static void vr_bfs(Session *s, const VrIndex &ixr, int64_t m, int upper, bool in
   }
 }
 
-DataPtr var_length_reach_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m,
-                                const ColPtr &sid, int64_t ns_in, const ColPtr &tid, int64_t nt,
-                                int lower, int upper) {
+static DataPtr vr_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m, const ColPtr &sid,
+                       int64_t ns_in, const ColPtr &tid, int64_t nt, int lower, int upper, bool undirected) {
   const bool include_self = lower == 0;
   auto out = std::make_shared<Data>();
   out->cols = {make_column(s, Type::Int64, 0, false), make_column(s, Type::Int64, 0, false)};
@@ -760,11 +1033,12 @@ DataPtr var_length_reach_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst
   // CAPF_VT_MAX_NODES (tests): a lower node limit of the trail kernel
   const char *vm = getenv("CAPF_VT_MAX_NODES");
   const int64_t vt_max = vm && atoll(vm) > 0 ? std::min<int64_t>(atoll(vm), VT_MAX_NODES) : VT_MAX_NODES;
-  if (lower >= 2 && ((int64_t)D > vt_max || m >= (int64_t(1) << 31))) return nullptr;
+  if ((undirected || lower >= 2) && ((int64_t)D > vt_max || m >= (int64_t(1) << 31))) return nullptr;
   const uint64_t *dk = (const uint64_t *)ix->dict->p;
   const BufPtr &src_nodes = ix->src_nodes;
   BufPtr reach = s->alloc(8 * std::max<int64_t>(ns, 1));
-  if (lower >= 2) vt_reach(s, *ix, m, lower, upper, (int64_t *)reach->p);
+  if (undirected) vu_reach(s, *ix, m, lower, upper, (int64_t *)reach->p);
+  else if (lower >= 2) vt_reach(s, *ix, m, lower, upper, (int64_t *)reach->p);
   else vr_bfs(s, *ix, m, upper, include_self, reach);
   // 5. rows (a, reach) for the sources that reach at least one target (every
   // source from lower bound 0)
@@ -787,6 +1061,19 @@ DataPtr var_length_reach_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst
   return out;
 }
 
+DataPtr var_length_reach_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m,
+                                const ColPtr &sid, int64_t ns_in, const ColPtr &tid, int64_t nt,
+                                int lower, int upper) {
+  return vr_rows(s, rsrc, rdst, m, sid, ns_in, tid, nt, lower, upper, false);
+}
+
+DataPtr var_length_reach_undirected_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m,
+                                           const ColPtr &sid, int64_t ns_in, const ColPtr &tid, int64_t nt,
+                                           int lower, int upper) {
+  if (lower < 0 || lower > upper || upper > 4) return nullptr;
+  return vr_rows(s, rsrc, rdst, m, sid, ns_in, tid, nt, lower, upper, true);
+}
+
 static ColPtr int_column_of(const NodePtr &nd, const DataPtr &d, const char *name) {
   const ColPtr &c = d->cols[nd->col_index_or_throw(name)];
   force(c);
@@ -799,20 +1086,23 @@ static ColPtr int_column_of(const NodePtr &nd, const DataPtr &d, const char *nam
 
 using namespace capf;
 
-extern "C" capf_status capf_var_length_reach(capf_session *cs, capf_table *rels, const char *src_col,
-                                             const char *dst_col, capf_table *sources,
-                                             const char *source_id_col, capf_table *targets,
-                                             const char *target_id_col, int32_t lower, int32_t upper,
-                                             const char *out_source_col, const char *out_reach_col,
-                                             capf_table **out) {
+static capf_status vr_entry(capf_session *cs, capf_table *rels, const char *src_col, const char *dst_col,
+                            capf_table *sources, const char *source_id_col, capf_table *targets,
+                            const char *target_id_col, int32_t lower, int32_t upper, const char *out_source_col,
+                            const char *out_reach_col, capf_table **out, bool undirected) {
   try {
     if (!cs || !rels || !src_col || !dst_col || !sources || !source_id_col || !targets ||
         !target_id_col || !out_source_col || !out_reach_col || !out)
       illegal("null argument");
-    if (lower < 0) not_impl("var-length reach: negative lower bound");
-    if (lower >= 2 && !(lower <= upper && upper <= 4))
-      not_impl("var-length reach: lower bounds from 2 are fused for 2 <= lower <= upper <= 4 only");
-    if (upper < 1 || upper > 64) illegal("var-length reach: upper bound out of range");
+    if (undirected) {
+      if (!(0 <= lower && lower <= upper && upper <= 4))
+        not_impl("undirected var-length reach is fused for 0 <= lower <= upper <= 4 only");
+    } else {
+      if (lower < 0) not_impl("var-length reach: negative lower bound");
+      if (lower >= 2 && !(lower <= upper && upper <= 4))
+        not_impl("var-length reach: lower bounds from 2 are fused for 2 <= lower <= upper <= 4 only");
+      if (upper < 1 || upper > 64) illegal("var-length reach: upper bound out of range");
+    }
     if (!strcmp(out_source_col, out_reach_col)) illegal("output column names must differ");
     Session *s = &cs->impl;
     DataPtr dr = materialize(rels->node), ds = materialize(sources->node),
@@ -820,8 +1110,12 @@ extern "C" capf_status capf_var_length_reach(capf_session *cs, capf_table *rels,
     ColPtr rs = int_column_of(rels->node, dr, src_col), rd = int_column_of(rels->node, dr, dst_col);
     ColPtr si = int_column_of(sources->node, ds, source_id_col);
     ColPtr ti = int_column_of(targets->node, dt, target_id_col);
-    DataPtr d = var_length_reach_rows(s, rs, rd, dr->nrows, si, ds->nrows, ti, dt->nrows, lower, upper);
-    if (!d) not_impl("var-length reach: more nodes than the trail kernel's LDS bitmap holds (2^20)");
+    DataPtr d = undirected ? var_length_reach_undirected_rows(s, rs, rd, dr->nrows, si, ds->nrows, ti, dt->nrows,
+                                                              lower, upper)
+                           : var_length_reach_rows(s, rs, rd, dr->nrows, si, ds->nrows, ti, dt->nrows, lower, upper);
+    if (!d)
+      not_impl(undirected ? "undirected var-length reach: more nodes than the step kernel's LDS bitmap holds (2^20)"
+                          : "var-length reach: more nodes than the trail kernel's LDS bitmap holds (2^20)");
     auto n = std::make_shared<Node>();
     n->s = s;
     n->kind = Kind::Source;
@@ -835,4 +1129,24 @@ extern "C" capf_status capf_var_length_reach(capf_session *cs, capf_table *rels,
   } catch (const capf::Error &e) {
     return record_error(e.code, e.what());
   }
+}
+
+extern "C" capf_status capf_var_length_reach(capf_session *cs, capf_table *rels, const char *src_col,
+                                             const char *dst_col, capf_table *sources,
+                                             const char *source_id_col, capf_table *targets,
+                                             const char *target_id_col, int32_t lower, int32_t upper,
+                                             const char *out_source_col, const char *out_reach_col,
+                                             capf_table **out) {
+  return vr_entry(cs, rels, src_col, dst_col, sources, source_id_col, targets, target_id_col, lower, upper,
+                  out_source_col, out_reach_col, out, false);
+}
+
+extern "C" capf_status capf_var_length_reach_undirected(capf_session *cs, capf_table *rels, const char *src_col,
+                                                        const char *dst_col, capf_table *sources,
+                                                        const char *source_id_col, capf_table *targets,
+                                                        const char *target_id_col, int32_t lower,
+                                                        int32_t upper, const char *out_source_col,
+                                                        const char *out_reach_col, capf_table **out) {
+  return vr_entry(cs, rels, src_col, dst_col, sources, source_id_col, targets, target_id_col, lower, upper,
+                  out_source_col, out_reach_col, out, true);
 }

@@ -234,6 +234,19 @@ class GpuSession:
                   out_source_col.encode(), out_reach_col.encode(), byref(h))
         return GpuTable(self, h)
 
+    def var_length_reach_undirected(self, rels, src_col, dst_col, sources, source_id_col, targets,
+                                    target_id_col, lower, upper, out_source_col, out_reach_col):
+        """The same fused operators over the undirected pattern (a)-[r*lower..upper]-(b)
+        (capf_var_length_reach_undirected): the (node, mode) steps of the
+        undirected lowering with pairwise distinct rels, enumerated per source.
+        0 <= lower <= upper <= 4, at most 2^20 distinct ids; other bounds raise
+        NotImplementedException."""
+        h = c_void_p()
+        _lib.call("capf_var_length_reach_undirected", self._h, rels._h, src_col.encode(), dst_col.encode(),
+                  sources._h, source_id_col.encode(), targets._h, target_id_col.encode(), int(lower), int(upper),
+                  out_source_col.encode(), out_reach_col.encode(), byref(h))
+        return GpuTable(self, h)
+
     # -- profiling ----------------------------------------------------------
     def set_profiling(self, on):
         _lib.call("capf_session_set_profiling", self._h, 1 if on else 0)

@@ -266,7 +266,8 @@ capf_status capf_session_profile_entry(capf_session *s, int32_t i, const char **
                                        int64_t *launches, double *total_ms, double *bytes);
 /* last fused execution path taken ("fused_chain2", "fused_triangle", "message_passing",
  * "fused_var_length_reach" (lower bound 0 / 1: BFS), "fused_var_length_trails"
- * (lower bound >= 2: trail enumeration); "none" until one runs) */
+ * (lower bound >= 2: trail enumeration), "fused_var_length_undirected" (undirected
+ * pattern: step enumeration); "none" until one runs) */
 const char *capf_session_last_plan(capf_session *s);
 
 /* String dictionary for CAPF_TYPE_STRING columns. */
@@ -485,6 +486,29 @@ capf_status capf_var_length_reach(capf_session *s, capf_table *rels, const char 
                                   const char *target_id_col, int32_t lower, int32_t upper,
                                   const char *out_source_col, const char *out_reach_col,
                                   capf_table **out);
+/* The same three operators over the UNDIRECTED pattern (a)-[r*lower..upper]-(b),
+ * as UndirectedVarLengthExpandPlanner lowers it (VarLengthExpandPlanner.scala:277-307):
+ * an automaton over states (node x, mode out | in) that starts at (a, out);
+ * a relationship e not yet on the path leads
+ *   (x, out), start(e) = x  ->  (end(e), out)
+ *   (x, out), end(e) = x    ->  (start(e), in)
+ *   (x, in),  start(e) = x  ->  (x, in)
+ *   (x, in),  end(e) = x    ->  (x, out)
+ * (after an inbound step the next step does not move), and every state reached
+ * at depth max(lower, 1)..upper pairs a with its node when that node is a
+ * target; lower = 0 adds (a, a) for every source.  Relationships on one path
+ * are pairwise distinct rows of `rels` (parallel rows differ, a self-loop row
+ * is one relationship, found from both of its node's sides).  This is neither
+ * a walk nor a trail of the symmetrised graph, so every bound is answered by
+ * per-source enumeration: 0 <= lower <= upper <= 4, at most 2^20 nodes in the
+ * id dictionary.  Other bounds, and a larger dictionary, return
+ * CAPF_ERR_NOT_IMPLEMENTED and the caller plans the join chain.            */
+capf_status capf_var_length_reach_undirected(capf_session *s, capf_table *rels, const char *src_col,
+                                             const char *dst_col, capf_table *sources,
+                                             const char *source_id_col, capf_table *targets,
+                                             const char *target_id_col, int32_t lower, int32_t upper,
+                                             const char *out_source_col, const char *out_reach_col,
+                                             capf_table **out);
 
 /* ------------------------------------------------ multi-GPU partial counts
  * Building blocks of the hash-partitioned 2-hop count: the

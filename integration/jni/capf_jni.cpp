@@ -614,6 +614,20 @@ JNI(jlong, varLengthReach)(JNIEnv *env, jobject, jlong s, jlong rels, jstring sr
              : H(out);
 }
 
+// the undirected pattern (VarLengthExpandPlanner.scala:277-307)
+JNI(jlong, varLengthReachUndirected)(JNIEnv *env, jobject, jlong s, jlong rels, jstring src_col,
+                                     jstring dst_col, jlong sources, jstring source_id, jlong targets,
+                                     jstring target_id, jint lower, jint upper, jstring out_source,
+                                     jstring out_reach) {
+  JStr a(env, src_col), b(env, dst_col), si(env, source_id), ti(env, target_id),
+      os(env, out_source), orr(env, out_reach);
+  capf_table *out = nullptr;
+  return fail(env, capf_var_length_reach_undirected(S(s), T(rels), a.p, b.p, T(sources), si.p,
+                                                    T(targets), ti.p, lower, upper, os.p, orr.p, &out))
+             ? 0
+             : H(out);
+}
+
 // ---------------------------------------------------------------- multi-GPU
 JNI(jlong, tableNodePartition)(JNIEnv *env, jobject, jlong t, jstring key_col, jlong node_base,
                                jlong n_nodes, jint parts, jint part) {

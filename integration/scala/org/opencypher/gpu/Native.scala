@@ -159,6 +159,9 @@ object Native {
   @native def varLengthReach(session: Long, rels: Long, srcCol: String, dstCol: String, sources: Long,
                              sourceId: String, targets: Long, targetId: String, lower: Int, upper: Int,
                              outSource: String, outReach: String): Long
+  @native def varLengthReachUndirected(session: Long, rels: Long, srcCol: String, dstCol: String, sources: Long,
+                                       sourceId: String, targets: Long, targetId: String, lower: Int, upper: Int,
+                                       outSource: String, outReach: String): Long
 
   // multi-GPU building blocks (one JVM per GPU; the caller all-reduces the device partials)
   @native def tableNodePartition(table: Long, keyCol: String, nodeBase: Long, nNodes: Long, parts: Int,
