@@ -106,6 +106,7 @@ _SIGS = {
     "capf_table_download": (c_int32, [_T, c_char_p, c_void_p, c_void_p]),
     "capf_table_list_info": (c_int32, [_T, c_char_p, POINTER(c_int32), POINTER(c_int64)]),
     "capf_table_download_list": (c_int32, [_T, c_char_p, c_void_p, c_void_p, c_void_p]),
+    "capf_table_download_list_nulls": (c_int32, [_T, c_char_p, c_void_p, POINTER(c_int32)]),
     "capf_table_device_column": (c_int32, [_T, c_char_p, POINTER(c_void_p), POINTER(c_void_p),
                                            POINTER(c_int64)]),
     "capf_table_cache": (c_int32, [_T, _PT]),
@@ -179,6 +180,7 @@ _SIGS = {
     "capf_session_code_map": (c_int32, [_S, POINTER(c_int64), c_int64, POINTER(c_int32)]),
     "capf_session_code_map_extend": (c_int32, [_S, c_int32, POINTER(c_int64), c_int64, POINTER(c_int32)]),
     "capf_table_add_list": (c_int32, [_T, c_char_p, c_int32, c_void_p, c_void_p, c_void_p, _PT]),
+    "capf_table_add_list_nulls": (c_int32, [_T, c_char_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, _PT]),
     "capf_table_name_list": (c_int32, [_T, c_int32, _STRS, POINTER(c_int32), POINTER(c_int64), c_char_p, _PT]),
     "capf_table_list_columns": (c_int32, [_T, c_int32, _STRS, c_char_p, _PT]),
     "capf_session_value_map": (c_int32, [_S, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_int64,

@@ -123,7 +123,10 @@ struct Column {
   // physical bits; a gather of it is a fill (no index read)
   bool is_const = false;
   uint64_t const_bits = 0;
-  // Type::List: the element column (never lazy, no NULL elements)
+  // Type::List: the element column (never lazy).  Its `valid` marks NULL
+  // elements and is absent when no element can be NULL; a list of NULL-typed
+  // items has a Type::Null child whose n is the element count (the offsets
+  // give the lengths)
   std::shared_ptr<Column> child;
   // an index derived from this column and a peer column (the triangle
   // count's oriented CSR of (this, peer)), built on first use and kept for

@@ -563,7 +563,11 @@ static ColPtr concat_lists(Session *s, const ColPtr &a, const ColPtr &b) {
     if (cb->type != Type::Null && cb->type != et)
       illegal(std::string("Equal column types for union all: LIST(") + type_name(ca->type) + ") vs LIST(" +
               type_name(cb->type) + ")");
-    child = concat_columns(s, ca, cb, et);
+    // a NULL-typed side with elements (`[null, null]`) gives that many NULL
+    // elements; without elements it adds nothing (and no validity)
+    if (ca->type == Type::Null && ca->n == 0) child = cb;
+    else if (cb->type == Type::Null && cb->n == 0) child = ca;
+    else child = concat_columns(s, ca, cb, et);
   } else {  // one side holds no elements: the other's element column as is
     child = ca ? ca : cb ? cb : null_column(s, Type::Null, 0);
   }
@@ -1365,8 +1369,8 @@ static DeviceProgram upload_program(Session *s, const Program &p,
         if (names[k] == p.names[(size_t)in.i]) idx = (int)k;
       if (idx < 0) illegal("expression references unknown column '" + p.names[(size_t)in.i] + "'");
       const ColPtr &c = d.cols[idx];
-      if (c->type != Type::List || !c->child) {
-        in.f = -1.0;  // a NULL-typed column: every row NULL
+      if (c->type != Type::List || !c->child || c->child->type == Type::Null) {
+        in.f = -1.0;  // a NULL-typed column, or NULL-typed elements: every row NULL
         continue;
       }
       force(c->child);

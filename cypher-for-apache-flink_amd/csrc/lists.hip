@@ -3,7 +3,8 @@
 // collect is the list-valued aggregator of the reference's Table SPI group
 // (Expr.scala Collect, lowered by FlinkSQLExprMapper.scala:283 to Flink's
 // COLLECT, a MULTISET).  A LIST column is CSR-shaped: int64 offsets [n + 1] in
-// `data` and the elements in `child` (a plain column, no NULL elements).
+// `data` and the elements in `child` (a plain column; its validity marks
+// NULL elements and is absent when none can occur).
 //   collect: keep the rows whose argument is non-NULL (compact_flags), drop
 //   duplicate (group, value) pairs for DISTINCT (group_rows), stable radix sort
 //   by (group, value) — elements ascend within a list —, per-group counts with
@@ -91,7 +92,7 @@ ColPtr collect_lists(Session *s, const Grouping &g, int64_t nrows, const ColPtr 
   auto child = std::make_shared<Column>();
   child->type = vs->type;
   child->n = k;
-  child->data = vs->data;  // no NULL elements: validity dropped
+  child->data = vs->data;  // collect keeps no NULLs: no element validity
   return list_column(s, ng, offsets, child);
 }
 
@@ -134,8 +135,10 @@ ColPtr gather_list(Session *s, const ColPtr &c, const int64_t *d_idx, int64_t m)
   KERNEL_CHECK();
   const int64_t total = exclusive_scan_i64(s, (const int64_t *)len->p, (int64_t *)noff->p, m + 1);
   ColPtr child;
-  if (total == 0 || c->child->type == Type::Null) {
+  if (total == 0) {
     child = empty_elements(s, c->child->type);
+  } else if (c->child->type == Type::Null) {  // NULL-typed elements: only their count
+    child = null_column(s, Type::Null, total);
   } else {
     BufPtr cidx = s->alloc(8 * total);
     hipLaunchKernelGGL(k_list_child_idx, dim3(grid_for(m, 256)), dim3(256), 0, s->stream, off, d_idx,
@@ -317,21 +320,49 @@ ColPtr name_list_column(Session *s, const Data &d, const std::vector<int> &cols,
 }
 
 // ------------------------------------------------- list literals per row
-// Element j of every row: child[i * k + j] = column j's value (an INTEGER
-// widened to FLOAT when the list's element type is FLOAT); a NULL element
-// raises the flag (LIST columns hold no NULL elements).
-__global__ void k_list_elem(ColView c, int64_t n, int32_t k, int32_t j, int32_t elem, void *child,
-                            uint32_t *null_seen) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    if (c.type == CAPF_TYPE_NULL || (c.valid && !c.valid[i])) null_seen[0] = 1u;
-    const int64_t o = i * k + j;
-    if (elem == CAPF_TYPE_BOOL) {
-      ((uint8_t *)child)[o] = c.data ? (((const uint8_t *)c.data)[i] ? 1 : 0) : 0;
-    } else if (elem == CAPF_TYPE_FLOAT64) {
-      ((double *)child)[o] = !c.data ? 0.0
-                             : c.type == CAPF_TYPE_FLOAT64 ? ((const double *)c.data)[i] : (double)ld_int(c, i);
+// Row i's list = (item 0's value, ..., item k-1's value): element o = i·k + j
+// of the child is item j at row i (an INTEGER widened to FLOAT when the
+// list's element type is FLOAT).  One launch, one thread per output element,
+// the item views passed by value: lane l stores child[o + l] (contiguous
+// 8-B / 1-B stores) and reads item j's rows in runs of ⌈64 / k⌉.  A NULL item
+// value stores 0 and validity 0; the validity bytes are written only when
+// some item can be NULL (cvalid non-null).  Literals longer than LI_MAX items
+// run in batches of items [j0, j0 + nb).  o / nb is taken once per thread:
+// the grid-stride step advances (i, j) by (stride / nb, stride % nb).
+constexpr int LI_MAX = 64;
+struct ListItems {
+  ColView c[LI_MAX];
+  int32_t nb;    // items of this batch
+  int32_t j0;    // first item of this batch
+  int32_t k;     // items of the literal (the row stride of the child)
+  int32_t elem;  // the list's element type
+};
+
+__global__ void k_list_fill(ListItems it, int64_t n, void *child, uint8_t *cvalid) {
+  const int64_t total = n * it.nb, stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= total) return;
+  int64_t i = o / it.nb;
+  int32_t j = (int32_t)(o - i * it.nb);
+  const int64_t di = stride / it.nb;
+  const int32_t dj = (int32_t)(stride - di * it.nb);
+  for (; o < total; o += stride) {
+    const ColView &c = it.c[j];
+    const bool ok = c.type != CAPF_TYPE_NULL && c.data && !(c.valid && !c.valid[i]);
+    const int64_t d = i * it.k + it.j0 + j;
+    if (it.elem == CAPF_TYPE_BOOL) {
+      ((uint8_t *)child)[d] = ok && ((const uint8_t *)c.data)[i] ? 1 : 0;
+    } else if (it.elem == CAPF_TYPE_FLOAT64) {
+      ((double *)child)[d] = !ok ? 0.0 : c.type == CAPF_TYPE_FLOAT64 ? ((const double *)c.data)[i] : (double)ld_int(c, i);
     } else {
-      ((int64_t *)child)[o] = c.data ? ld_int(c, i) : 0;
+      ((int64_t *)child)[d] = ok ? ld_int(c, i) : 0;
+    }
+    if (cvalid) cvalid[d] = ok ? 1 : 0;
+    i += di;
+    j += dj;
+    if (j >= it.nb) {
+      j -= it.nb;
+      ++i;
     }
   }
 }
@@ -348,21 +379,29 @@ ColPtr list_from_columns(Session *s, const Data &d, const std::vector<int> &cols
   hipLaunchKernelGGL(k_list_offsets_stride, dim3(grid_for(n + 1, 256)), dim3(256), 0, s->stream,
                      (int64_t *)off->p, n, k);
   KERNEL_CHECK();
-  ColPtr child = k == 0 ? empty_elements(s, elem) : make_column(s, elem, n * k, false);
-  if (n > 0 && k > 0) {
-    BufPtr flag = s->alloc(4);
-    HIP_CHECK(hipMemsetAsync(flag->p, 0, 4, s->stream));
-    for (int32_t j = 0; j < k; ++j) {
-      const ColPtr &c = d.cols[(size_t)cols[(size_t)j]];
-      const ColView v = c->type == Type::Null ? ColView{nullptr, nullptr, CAPF_TYPE_NULL, ENC_PLAIN, 0} : view_of(c);
-      hipLaunchKernelGGL(k_list_elem, dim3(grid_for(n, 256)), dim3(256), 0, s->stream, v, n, k, j, (int32_t)elem,
-                         child->data->p, (uint32_t *)flag->p);
+  if (k == 0) return list_column(s, n, off, empty_elements(s, elem));
+  // every item NULL-typed: n·k NULL elements, no buffers
+  if (elem == Type::Null) return list_column(s, n, off, null_column(s, Type::Null, n * k));
+  std::vector<ColView> views;
+  bool nullable = false;
+  for (int32_t j = 0; j < k; ++j) {
+    const ColPtr &c = d.cols[(size_t)cols[(size_t)j]];
+    views.push_back(c->type == Type::Null ? ColView{nullptr, nullptr, CAPF_TYPE_NULL, ENC_PLAIN, 0} : view_of(c));
+    nullable = nullable || c->type == Type::Null || c->valid;  // (view_of forced c)
+  }
+  ColPtr child = make_column(s, elem, n * k, nullable);
+  if (n > 0) {
+    for (int32_t j0 = 0; j0 < k; j0 += LI_MAX) {
+      ListItems it{};
+      it.nb = std::min<int32_t>(LI_MAX, k - j0);
+      it.j0 = j0;
+      it.k = k;
+      it.elem = (int32_t)elem;
+      for (int32_t j = 0; j < it.nb; ++j) it.c[j] = views[(size_t)(j0 + j)];
+      hipLaunchKernelGGL(k_list_fill, dim3(grid_for(n * it.nb, 256)), dim3(256), 0, s->stream, it, n,
+                         child->data->p, child->valid ? (uint8_t *)child->valid->p : nullptr);
       KERNEL_CHECK();
     }
-    uint32_t seen = 0;
-    HIP_CHECK(hipMemcpyAsync(&seen, flag->p, 4, hipMemcpyDeviceToHost, s->stream));
-    s->sync();
-    if (seen) not_impl("a NULL element in a list (LIST columns hold no NULL elements)");
   }
   return list_column(s, n, off, child);
 }

@@ -1927,6 +1927,30 @@ capf_status capf_table_download_list(capf_table *t, const char *col, int64_t *of
   CAPF_API_END
 }
 
+capf_status capf_table_download_list_nulls(capf_table *t, const char *col, uint8_t *elem_valid_out,
+                                           int32_t *has_nulls) {
+  CAPF_API_BEGIN
+  need(t, "table");
+  need(col, "col");
+  need(has_nulls, "has_nulls");
+  int i = t->node->col_index_or_throw(col);
+  if (t->node->types[i] != Type::List) illegal("column '" + std::string(col) + "' is not a LIST");
+  DataPtr d = materialize(t->node);
+  const ColPtr &c = d->cols[i];
+  Session *s = t->node->s;
+  const ColPtr &ch = c->child;
+  *has_nulls = ch->type == Type::Null || ch->valid ? 1 : 0;
+  if (*has_nulls && elem_valid_out && ch->n > 0) {
+    if (ch->type == Type::Null) {
+      memset(elem_valid_out, 0, (size_t)ch->n);
+    } else {
+      HIP_CHECK(hipMemcpyAsync(elem_valid_out, ch->valid->p, (size_t)ch->n, hipMemcpyDeviceToHost, s->stream));
+      s->sync();
+    }
+  }
+  CAPF_API_END
+}
+
 capf_status capf_table_device_column(capf_table *t, const char *col, void **values,
                                      uint8_t **valid, int64_t *nrows) {
   CAPF_API_BEGIN
@@ -2296,14 +2320,17 @@ capf_status capf_table_explode_values(capf_table *t, const char *name, int32_t t
   CAPF_API_END
 }
 
-capf_status capf_table_add_list(capf_table *t, const char *name, int32_t elem_type, const int64_t *offsets,
-                                const void *values, const uint8_t *valid, capf_table **out) {
-  CAPF_API_BEGIN
+// capf_table_add_list / _nulls: elem_valid (nv bytes) marks NULL elements; a
+// NULL-typed element column holds only its count
+static void add_list_column(capf_table *t, const char *name, int32_t elem_type, const int64_t *offsets,
+                            const void *values, const uint8_t *valid, const uint8_t *elem_valid, bool null_elems,
+                            capf_table **out) {
   need(t, "table");
   need(name, "name");
   need(offsets, "offsets");
   need(out, "out");
-  if (elem_type < CAPF_TYPE_INT64 || elem_type > CAPF_TYPE_STRING) illegal("bad list element type");
+  if (elem_type < (null_elems ? CAPF_TYPE_NULL : CAPF_TYPE_INT64) || elem_type > CAPF_TYPE_STRING)
+    illegal("bad list element type");
   const NodePtr &c = t->node;
   if (c->col_index(name) >= 0) illegal(std::string("column '") + name + "' already exists");
   DataPtr d = materialize(c);
@@ -2313,10 +2340,13 @@ capf_status capf_table_add_list(capf_table *t, const char *name, int32_t elem_ty
   for (int64_t i = 0; i < n; ++i)
     if (offsets[i + 1] < offsets[i]) illegal("list offsets must not decrease");
   const int64_t nv = offsets[n];
-  if (nv > 0 && !values) illegal("list values missing");
   const Type et = (Type)elem_type;
-  auto child = make_column(s, et, nv, false);
-  if (nv > 0) HIP_CHECK(hipMemcpyAsync(child->data->p, values, type_width(et) * nv, hipMemcpyHostToDevice, s->stream));
+  if (nv > 0 && !values && et != Type::Null) illegal("list values missing");
+  auto child = et == Type::Null ? null_column(s, Type::Null, nv) : make_column(s, et, nv, elem_valid != nullptr);
+  if (nv > 0 && et != Type::Null) {
+    HIP_CHECK(hipMemcpyAsync(child->data->p, values, type_width(et) * nv, hipMemcpyHostToDevice, s->stream));
+    if (elem_valid) HIP_CHECK(hipMemcpyAsync(child->valid->p, elem_valid, (size_t)nv, hipMemcpyHostToDevice, s->stream));
+  }
   auto lc = std::make_shared<Column>();
   lc->type = Type::List;
   lc->n = n;
@@ -2339,6 +2369,20 @@ capf_status capf_table_add_list(capf_table *t, const char *name, int32_t elem_ty
   e->cols.push_back(lc);
   nn->result = e;
   *out = wrap(nn);
+}
+
+capf_status capf_table_add_list(capf_table *t, const char *name, int32_t elem_type, const int64_t *offsets,
+                                const void *values, const uint8_t *valid, capf_table **out) {
+  CAPF_API_BEGIN
+  add_list_column(t, name, elem_type, offsets, values, valid, nullptr, false, out);
+  CAPF_API_END
+}
+
+capf_status capf_table_add_list_nulls(capf_table *t, const char *name, int32_t elem_type, const int64_t *offsets,
+                                      const void *values, const uint8_t *valid, const uint8_t *elem_valid,
+                                      capf_table **out) {
+  CAPF_API_BEGIN
+  add_list_column(t, name, elem_type, offsets, values, valid, elem_valid, true, out);
   CAPF_API_END
 }
 
@@ -2385,8 +2429,9 @@ capf_status capf_table_list_columns(capf_table *t, int32_t n, const char *const 
     const int idx = c->col_index_or_throw(cols[j]);
     const Type ct = c->types[(size_t)idx];
     if (ct == Type::List) not_impl("nested lists");
-    if (ct == Type::Null) not_impl("a NULL element in a list (LIST columns hold no NULL elements)");
-    if (et == Type::Null || et == ct) et = ct;
+    // a NULL-typed item is a NULL element: the element type is that of the
+    // other items (Type::Null when there are none)
+    if (ct == Type::Null || et == Type::Null || et == ct) et = ct == Type::Null ? et : ct;
     else if ((et == Type::Int64 || et == Type::Float64) && (ct == Type::Int64 || ct == Type::Float64))
       et = Type::Float64;  // INTEGER and FLOAT elements widen together
     else

@@ -370,8 +370,11 @@ class GpuTable:
                   valid.ctypes.data if n else None)
         return vals, valid.astype(bool)
 
-    def list_values(self, col):
-        """Python lists (None for a NULL list) of a LIST column (collect)."""
+    def list_arrays(self, col):
+        """The arrays of a LIST column: (element capf type, offsets int64
+        [size + 1], element values [n_values] (zeros for NULL-typed elements),
+        list validity uint8 [size], element validity uint8 [n_values] or None
+        when no element can be NULL)."""
         et, nv = c_int32(), c_int64()
         _lib.call("capf_table_list_info", self._h, col.encode(), byref(et), byref(nv))
         n = self.size
@@ -381,18 +384,38 @@ class GpuTable:
         vals = np.zeros(max(nv.value, 1), dtype=_NP_DTYPE.get(t, np.int64))
         _lib.call("capf_table_download_list", self._h, col.encode(), offs.ctypes.data,
                   vals.ctypes.data if nv.value and t != T_NULL else None, valid.ctypes.data if n else None)
+        return t, offs, vals[:nv.value], valid[:n], self.list_elem_valid(col, nv.value)
+
+    def list_values(self, col):
+        """Python lists (None for a NULL list, None for a NULL element) of a
+        LIST column."""
+        t, offs, vals, valid, ev = self.list_arrays(col)
         out = []
-        for i in range(n):
+        for i in range(len(valid)):
             if not valid[i]:
                 out.append(None)
                 continue
             xs = vals[offs[i]:offs[i + 1]].tolist()
+            if ev is not None:  # NULL elements
+                xs = [x if ok else None for x, ok in zip(xs, ev[offs[i]:offs[i + 1]].tolist())]
             if t == T_STRING:
-                xs = [self.session.lookup(x) for x in xs]
+                xs = [None if x is None else self.session.lookup(x) for x in xs]
             elif t == T_BOOL:
-                xs = [bool(x) for x in xs]
+                xs = [None if x is None else bool(x) for x in xs]
             out.append(xs)
         return out
+
+    def list_elem_valid(self, col, n_values):
+        """Element validity of a LIST column (capf_table_download_list_nulls):
+        a uint8 array of n_values entries, 0 = a NULL element, or None when the
+        column carries none (no element is NULL)."""
+        has = c_int32()
+        _lib.call("capf_table_download_list_nulls", self._h, col.encode(), None, byref(has))
+        if not has.value:
+            return None
+        ev = np.zeros(max(n_values, 1), dtype=np.uint8)
+        _lib.call("capf_table_download_list_nulls", self._h, col.encode(), ev.ctypes.data, byref(has))
+        return ev[:n_values]
 
     def column_values(self, col):
         """Python values (None for NULL) of one column."""
@@ -551,30 +574,42 @@ class GpuTable:
     def add_list(self, name, values, valid=None):
         """This table plus LIST column `name` from host lists (None = a NULL
         list): capf_table_add_list.  INTEGER and FLOAT elements widen to FLOAT
-        together; NULL elements are NotImplemented (LIST columns hold none)."""
-        kinds = set()
+        together.  None elements are NULL elements (capf_table_add_list_nulls:
+        the element type is that of the others, T_NULL when there are none)."""
+        kinds, nulls = set(), False
         for xs in values:
             for x in xs or ():
                 if x is None:
-                    raise _lib.NotImplementedException("NULL elements in a LIST property")
+                    nulls = True
+                    continue
                 kinds.add(T_BOOL if isinstance(x, bool) else T_INT if isinstance(x, int) else
                           T_FLOAT if isinstance(x, float) else T_STRING if isinstance(x, str) else None)
         if None in kinds or len(kinds - {T_INT, T_FLOAT}) > (0 if kinds & {T_INT, T_FLOAT} else 1):
             raise _lib.NotImplementedException(f"LIST property '{name}' of mixed or nested elements")
-        et = T_FLOAT if T_FLOAT in kinds else kinds.pop() if kinds else T_INT
+        et = T_FLOAT if T_FLOAT in kinds else kinds.pop() if kinds else T_NULL if nulls else T_INT
         offs = np.zeros(len(values) + 1, dtype=np.int64)
         flat = []
         for i, xs in enumerate(values):
             flat += list(xs or ())
             offs[i + 1] = len(flat)
-        if et == T_STRING:
-            data = np.array([self.session.intern(x) for x in flat], dtype=np.int64)
-        else:
-            data = np.array(flat, dtype=_NP_DTYPE[et]) if flat else np.zeros(1, dtype=_NP_DTYPE[et])
         ok = np.array([xs is not None for xs in values], dtype=np.uint8) if valid is None else \
             np.ascontiguousarray(np.asarray(valid, dtype=np.uint8))
-        return self._new("capf_table_add_list", self._h, name.encode(), int(et), offs.ctypes.data,
-                         data.ctypes.data, ok.ctypes.data if len(values) else None)
+        if nulls:  # a NULL element's slot holds 0
+            ev = np.array([x is not None for x in flat], dtype=np.uint8)
+            flat = [(0 if et == T_INT else 0.0 if et == T_FLOAT else False if et == T_BOOL else None)
+                    if x is None else x for x in flat]
+        if et == T_NULL:
+            data = None
+        elif et == T_STRING:
+            data = np.array([0 if x is None else self.session.intern(x) for x in flat], dtype=np.int64)
+        else:
+            data = np.array(flat, dtype=_NP_DTYPE[et]) if flat else np.zeros(1, dtype=_NP_DTYPE[et])
+        if not nulls:
+            return self._new("capf_table_add_list", self._h, name.encode(), int(et), offs.ctypes.data,
+                             data.ctypes.data, ok.ctypes.data if len(values) else None)
+        return self._new("capf_table_add_list_nulls", self._h, name.encode(), int(et), offs.ctypes.data,
+                         data.ctypes.data if data is not None else None, ok.ctypes.data if len(values) else None,
+                         ev.ctypes.data if et != T_NULL else None)
 
     def _value_map(self, kind, exprs, header, params):
         """Program name of a session value map (CAPF_OP_VALUE_MAP) giving the STRING

@@ -328,12 +328,21 @@ capf_status capf_table_download(capf_table *t, const char *col, void *values_out
  * keys, or a column passed through select / filter / join / union / sort).
  * capf_table_download_list: offsets_out[size + 1] (int64, list i = elements
  * [offsets[i], offsets[i+1])), values_out[n_values] elements (8 or 1 bytes
- * each, never NULL), valid_out[size] list validity (may be NULL).
+ * each; a NULL element's slot holds 0), valid_out[size] list validity (may
+ * be NULL).  A list whose elements are all NULL-typed (`[null, null]`) has
+ * element type CAPF_TYPE_NULL with n_values > 0: its offsets give its length,
+ * nothing is written to values_out.
+ * capf_table_download_list_nulls: which elements are NULL.  *has_nulls = 0
+ * when the element column carries no validity and is not NULL-typed (nothing
+ * is written); otherwise 1 and elem_valid_out[n_values] (1 = present, all 0
+ * for NULL-typed elements).  elem_valid_out may be NULL: *has_nulls alone.
  * capf_table_download of a LIST column is CAPF_ERR_ILLEGAL_ARGUMENT.        */
 capf_status capf_table_list_info(capf_table *t, const char *col, int32_t *elem_type,
                                  int64_t *n_values);
 capf_status capf_table_download_list(capf_table *t, const char *col, int64_t *offsets_out,
                                      void *values_out, uint8_t *valid_out);
+capf_status capf_table_download_list_nulls(capf_table *t, const char *col, uint8_t *elem_valid_out,
+                                           int32_t *has_nulls);
 /* Device view of a materialised column (for zero-copy interop). */
 capf_status capf_table_device_column(capf_table *t, const char *col, void **values,
                                      uint8_t **valid, int64_t *nrows);
@@ -411,9 +420,10 @@ capf_status capf_table_with_columns(capf_table *t, int32_t n, const capf_expr *e
  * capf_table_explode_values: the same literal / parameter list for every row:
  *   n elements of capf type `type` (INT64 / FLOAT64 / BOOL / STRING codes /
  *   NULL), values n × (8 or 1) bytes (NULL for a NULL-typed list), valid
- *   NULL (no NULL elements) or n bytes.
+ *   a NULL pointer (every element present) or n bytes (0 = a NULL element).
  * capf_table_explode_list: the elements of LIST column list_col (a NULL list
- *   drops the row, like an empty one).  Lazy like every other operator: t is
+ *   drops the row, like an empty one; a NULL element is a row whose `name`
+ *   is NULL).  Lazy like every other operator: t is
  *   evaluated with the result, unless list_col is a computed list expression
  *   (its element type is then only known once it exists).                  */
 capf_status capf_table_explode_values(capf_table *t, const char *name, int32_t type, int64_t n,
@@ -692,17 +702,25 @@ capf_status capf_session_code_map_extend(capf_session *s, int32_t map_id, const 
  * ARRAY column): appends LIST column `name` to t's rows (t is materialised):
  * row i holds values[offsets[i] .. offsets[i + 1]) (offsets: size + 1 int64,
  * offsets[0] = 0), elements of capf type elem_type (INTEGER / FLOAT / BOOLEAN
- * / STRING codes, 8 B each, BOOLEAN 1 B; no NULL elements); valid (size
- * bytes or NULL): 0 = a NULL list.                                         */
+ * / STRING codes, 8 B each, BOOLEAN 1 B; every element present); valid (size
+ * bytes or NULL): 0 = a NULL list.
+ * capf_table_add_list_nulls: the same with element validity elem_valid
+ * (offsets[size] bytes, 0 = a NULL element, or NULL: every element present).
+ * elem_type may be CAPF_TYPE_NULL with values NULL: every element is NULL.  */
 capf_status capf_table_add_list(capf_table *t, const char *name, int32_t elem_type, const int64_t *offsets,
                                 const void *values, const uint8_t *valid, capf_table **out);
+capf_status capf_table_add_list_nulls(capf_table *t, const char *name, int32_t elem_type, const int64_t *offsets,
+                                      const void *values, const uint8_t *valid, const uint8_t *elem_valid,
+                                      capf_table **out);
 
 /* This table plus LIST column `name` whose row i holds (cols[0][i], ...,
  * cols[n-1][i]) — a list literal of per-row elements, `[n.val * 10, $p]`
  * (replaces FlinkSQLExprMapper.scala:71 `array(...)` over the converted
- * children).  The element columns share one type (INTEGER and FLOAT widen to
- * FLOAT); a NULL-typed or NULL-holding element is NotImplemented (LIST columns
- * hold no NULL elements), as are nested lists.  n = 0: the empty list.       */
+ * children).  The non-NULL-typed element columns share one type (INTEGER and
+ * FLOAT widen to FLOAT), the list's element type; CAPF_TYPE_NULL when every
+ * item is NULL-typed.  A NULL item value is a NULL element (the element
+ * column then carries validity; without nullable items it carries none).
+ * Nested lists are NotImplemented.  n = 0: the empty list.                  */
 capf_status capf_table_list_columns(capf_table *t, int32_t n, const char *const *cols, const char *name,
                                     capf_table **out);
 /* labels(n) / keys(n) (FlinkSQLExprMapper.scala:136-153; the GetLabels /

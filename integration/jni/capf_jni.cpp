@@ -377,6 +377,15 @@ JNI(void, tableDownloadList)(JNIEnv *env, jobject, jlong t, jstring col, jobject
   fail(env, capf_table_download_list(T(t), c.p, (int64_t *)direct(env, offsets), direct(env, values),
                                      (uint8_t *)direct(env, valid)));
 }
+// NULL elements of a LIST column: returns 1 when the element column carries
+// validity (or is NULL-typed) and fills elemValid (n_values bytes, 1 = present;
+// may be null to ask only), 0 when no element is NULL (nothing written)
+JNI(jint, tableDownloadListNulls)(JNIEnv *env, jobject, jlong t, jstring col, jobject elemValid) {
+  JStr c(env, col);
+  int32_t has = 0;
+  if (fail(env, capf_table_download_list_nulls(T(t), c.p, (uint8_t *)direct(env, elemValid), &has))) return 0;
+  return has;
+}
 // device view: out = {values, valid, nrows}
 JNI(void, tableDeviceColumn)(JNIEnv *env, jobject, jlong t, jstring col, jlongArray out) {
   JStr c(env, col);
@@ -530,6 +539,22 @@ JNI(jlong, tableAddList)(JNIEnv *env, jobject, jlong t, jstring name, jint elem_
   return fail(env, capf_table_add_list(T(t), nm.p, elem_type, (const int64_t *)direct(env, offsets),
                                        values ? direct(env, values) : nullptr,
                                        valid ? (const uint8_t *)direct(env, valid) : nullptr, &out))
+             ? 0
+             : H(out);
+}
+// the same with element validity (offsets[size] bytes, 0 = a NULL element) or
+// null; elem_type CAPF_TYPE_NULL with values null: every element is NULL
+JNI(jlong, tableAddListNulls)(JNIEnv *env, jobject, jlong t, jstring name, jint elem_type, jobject offsets,
+                              jobject values, jobject valid, jobject elemValid) {
+  JStr nm(env, name);
+  if (!offsets || !direct(env, offsets)) {
+    illegal_argument(env, "tableAddListNulls: offsets must be a direct buffer");
+    return 0;
+  }
+  capf_table *out = nullptr;
+  return fail(env, capf_table_add_list_nulls(T(t), nm.p, elem_type, (const int64_t *)direct(env, offsets),
+                                             direct(env, values), (const uint8_t *)direct(env, valid),
+                                             (const uint8_t *)direct(env, elemValid), &out))
              ? 0
              : H(out);
 }

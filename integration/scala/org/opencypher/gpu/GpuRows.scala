@@ -85,8 +85,59 @@ object GpuRows {
       case Native.TypeString => CypherString(Native.guard(Native.stringLookup(t.session.handle, values.getLong(8 * k))))
       case _ => CypherNull
     }
+    // NULL elements (capf_table_download_list_nulls): present only when the element column carries validity
+    val elemValid = ByteBuffer.allocateDirect(math.max(1, nv(0).toInt))
+    val hasNulls = Native.guard(Native.tableDownloadListNulls(t.handle, c, elemValid)) != 0
+    def element(k: Int): CypherValue = if (hasNulls && elemValid.get(k) == 0) CypherNull else value(k)
     i =>
       if (valid.get(i) == 0) CypherNull
-      else CypherList((offsets.getLong(8 * i).toInt until offsets.getLong(8 * (i + 1)).toInt).map(value): _*)
+      else CypherList((offsets.getLong(8 * i).toInt until offsets.getLong(8 * (i + 1)).toInt).map(element): _*)
+  }
+
+  /** A LIST column from host lists (capf_table_add_list / _nulls): CypherNull rows are NULL lists, CypherNull
+    * elements NULL elements; the element type is that of the other elements (INTEGER and FLOAT widen to FLOAT),
+    * NULL-typed when there are none.  Returns the new handle. */
+  def addList(t: GpuTable, col: String, rows: Seq[CypherValue]): Long = {
+    val lists: Seq[Option[Seq[CypherValue]]] = rows.map {
+      case CypherList(vs) => Some(vs)
+      case CypherNull => None
+      case other => throw new UnsupportedOperationException(s"LIST column value $other")
+    }
+    val flat = lists.flatMap(_.getOrElse(Seq.empty))
+    val present = flat.filter(_ != CypherNull)
+    val ty =
+      if (present.isEmpty) { if (flat.isEmpty) Native.TypeInt64 else Native.TypeNull }
+      else if (present.forall(_.isInstanceOf[CypherInteger])) Native.TypeInt64
+      else if (present.forall(v => v.isInstanceOf[CypherInteger] || v.isInstanceOf[CypherFloat])) Native.TypeFloat64
+      else if (present.forall(_.isInstanceOf[CypherBoolean])) Native.TypeBool
+      else if (present.forall(_.isInstanceOf[CypherString])) Native.TypeString
+      else throw new UnsupportedOperationException(s"LIST column '$col' of mixed or nested elements")
+    val n = lists.size
+    val width = if (ty == Native.TypeBool) 1 else 8
+    val offsets = ByteBuffer.allocateDirect(8 * (n + 1)).order(ByteOrder.nativeOrder())
+    val valid = ByteBuffer.allocateDirect(math.max(1, n))
+    var total = 0L
+    offsets.putLong(0, 0L)
+    lists.zipWithIndex.foreach { case (xs, i) =>
+      total += xs.map(_.size).getOrElse(0)
+      offsets.putLong(8 * (i + 1), total)
+      valid.put(i, if (xs.isDefined) 1.toByte else 0.toByte)
+    }
+    val values = ByteBuffer.allocateDirect(math.max(1, flat.size * width)).order(ByteOrder.nativeOrder())
+    val elemValid = ByteBuffer.allocateDirect(math.max(1, flat.size))
+    flat.zipWithIndex.foreach { case (v, k) =>
+      elemValid.put(k, if (v == CypherNull) 0.toByte else 1.toByte)
+      v match {
+        case CypherInteger(x) if ty == Native.TypeFloat64 => values.putDouble(8 * k, x.toDouble)
+        case CypherInteger(x) => values.putLong(8 * k, x)
+        case CypherFloat(x) => values.putDouble(8 * k, x)
+        case CypherBoolean(b) => values.put(k, if (b) 1.toByte else 0.toByte)
+        case CypherString(s) => values.putLong(8 * k, Native.guard(Native.stringIntern(t.session.handle, s)))
+        case _ =>  // a NULL element's slot stays 0
+      }
+    }
+    if (present.size == flat.size) Native.guard(Native.tableAddList(t.handle, col, ty, offsets, values, valid))
+    else Native.guard(Native.tableAddListNulls(t.handle, col, ty, offsets,
+      if (ty == Native.TypeNull) null else values, valid, if (ty == Native.TypeNull) null else elemValid))
   }
 }

@@ -110,6 +110,8 @@ object Native {
   @native def tableListInfo(table: Long, col: String, nValuesOut: Array[Long]): Int
   @native def tableDownloadList(table: Long, col: String, offsets: ByteBuffer, values: ByteBuffer,
                                 valid: ByteBuffer): Unit
+  // 1: elemValid (n_values bytes, 0 = a NULL element; may be null) filled; 0: no element is NULL
+  @native def tableDownloadListNulls(table: Long, col: String, elemValid: ByteBuffer): Int
   @native def tableDeviceColumn(table: Long, col: String, out: Array[Long]): Unit
   @native def tableCompact(table: Long): Long
   @native def tableCompactWidth(table: Long, width: Int): Long
@@ -140,6 +142,10 @@ object Native {
   // a LIST property column (CTList) from direct buffers: offsets, element values, list validity
   @native def tableAddList(table: Long, name: String, elemType: Int, offsets: java.nio.ByteBuffer,
                            values: java.nio.ByteBuffer, valid: java.nio.ByteBuffer): Long
+  // ... with element validity (0 = a NULL element); elemType TypeNull, values null: all elements NULL
+  @native def tableAddListNulls(table: Long, name: String, elemType: Int, offsets: java.nio.ByteBuffer,
+                                values: java.nio.ByteBuffer, valid: java.nio.ByteBuffer,
+                                elemValid: java.nio.ByteBuffer): Long
   @native def tableNameList(table: Long, cols: Array[String], kinds: Array[Int], codes: Array[Long], name: String): Long
   @native def tableListColumns(table: Long, cols: Array[String], name: String): Long
   @native def tableShow(table: Long, rows: Int): Unit
