@@ -670,6 +670,8 @@ struct C2Spill {
   // with the out keys, no histograms stored): no dot kernel; log / n then hold
   // only the entries that overflowed a unit's LDS hot table (diagnostics)
   bool fin_written = false;
+  // probe mode: jobs of a bucket's out-run run by a unit other than its owner (diagnostics)
+  const uint32_t *steals = nullptr;
 };
 // d_acc3 = [Σ in·out, self-loops, done counter] (device): the pipeline writes
 // the self-loop total into [1] and clears [0] and [2] itself (no memset needed)

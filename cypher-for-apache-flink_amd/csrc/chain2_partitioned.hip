@@ -37,8 +37,12 @@
 //         atomics, no conflicts).  A counter reaching 2^15 hands off to a
 //         per-unit LDS hot table (the global log only when that is full);
 //         before the probe every half becomes in mod 2^16 and the few keys of
-//         in-degree ≥ 2^16 have their probes counted per wave.  Each unit adds
-//         its Σ and its share of the self-loops; the last one writes the count.
+//         in-degree ≥ 2^16 have their probes counted per wave.  The probe is a
+//         loop over jobs (bucket, tile range of its out-run): a unit runs its own
+//         out-run, then tile ranges of buckets whose (late) units published their
+//         finalised halves through HBM (C5Steal: nobody waits for anybody).
+//         Each unit adds its Σ and its share of the self-loops; the last one
+//         writes the count.
 // The other modes of the fused count
 // (C5PostPlan; the table of all seven is in DESIGN.md) add
 //   T  k_c3_transpose  [tile][run] → [run][tile] meta, per-run totals, Σ self-loops
@@ -617,12 +621,46 @@ __device__ inline void c3_handoff(uint32_t *w, uint32_t inc, uint32_t hidx, uint
 constexpr int C5_HOT = 512;  // hot-table slots
 constexpr uint32_t C5_HOT_EMPTY = 0xFFFFFFFFu;
 
+// Mode P, phase 2 shared between units.  A unit that publishes copies what
+// phase 2 reads of its bucket (the image: 2^16 halves, bucket id, special keys
+// and their extras) into a slot of the work area and hands its out-run out as
+// jobs of job_tiles tiles from the slot's cursor; a unit that has finished its
+// own bucket loads a ready slot's image into its LDS and takes jobs from that
+// cursor.  Nobody waits: a slot that is not ready yet is passed over.
+enum : uint32_t {
+  C5_STEAL_OFF = 0,
+  C5_STEAL_HEAVY = 1,  // units whose in-run or out-run exceeds heavy_pieces publish
+  C5_STEAL_ALL = 2,    // every unit publishes
+  C5_STEAL_RELOAD = 3  // (tests) every unit publishes and re-reads its own image before its first job
+};
+constexpr int C5_IMAGE_BYTES = 2 * C2_BW + 16 + 8 * 512;  // halves | (ns, bucket, 0, 0) | sk[512] | sx[512]
+constexpr int C5_HEAVY_SLOTS = 16;
+// Its arguments; steal = C5_STEAL_OFF: nothing else is read.
+// The unit parks these in LDS at its start: the job loop reads them between
+// walks, and as kernel arguments they would sit in SGPRs across the walks.
+struct C5Steal {
+  uint32_t steal;         // C5_STEAL_*
+  uint32_t job_tiles;     // tiles of an out-run per job
+  uint32_t nslots;        // image slots
+  uint32_t heavy_pieces;  // C5_STEAL_HEAVY: a unit publishes when a run of its holds more pieces
+  uint32_t *slots_used;   // slots claimed so far (may pass nslots: the late claimers do not publish)
+  uint32_t *steals;       // jobs run by a unit other than the bucket's owner (profile)
+  uint32_t *ready;        // [nslots] the slot's image is complete
+  uint32_t *cursor;       // [nslots] next job of the slot's out-run
+  uint4 *images;          // [nslots] × C5_IMAGE_BYTES
+};
+
 struct C5Probe {
   unsigned long long *acc3;    // [Σ in·out, self-loops, done]
   int64_t *fin;                // the count: the pinned host scalar or the async slot
   const uint32_t *tile_loops;  // P1's per-tile self-loop counts
   uint32_t hotcap;             // hot-table slots in use (1..C5_HOT; CAPF_C5_HOTCAP: tests)
+  C5Steal st;
 };
+
+// the unit's job mailbox in LDS (words)
+enum { CJ_SLOT, CJ_IDX, CJ_NEED, CJ_CUR, CJ_IMG, CJ_NSTEAL, CJ_BKT, CJ_PIN, CJ_POUT, CJ_MINE, CJ_WORDS = 12 };
+constexpr int CJ_NONE = -1, CJ_OWN = -2, CJ_OWN_PENDING = -3;
 
 __device__ inline void c5_log_append(uint2 *log, uint32_t *n, uint32_t cap, uint32_t gkey, uint32_t count) {
   const uint32_t k = atomicAdd(n, 1u);
@@ -679,8 +717,9 @@ struct C5WaveTab {
 constexpr size_t C5_GATHER_LDS =
     4 * (C2_WORDS + C5_CORR) + 2 * sizeof(C5WaveTab) * (C5_BLOCK / WAVE);
 // mode P: + the out side's correction bins, the hot table (keys, totals), the specials
-// (keys, extras), the block reduction, the specials' count and the hot pad bins' mask
-constexpr size_t C5_PROBE_LDS = C5_GATHER_LDS + 4 * C5_CORR + 16 * C5_HOT + 8 * 17 + 16;
+// (keys, extras), the block reduction, the specials' count, the hot pad bins' mask and the
+// job mailbox (a helped bucket's image replaces the unit's own halves, specials and count)
+constexpr size_t C5_PROBE_LDS = C5_GATHER_LDS + 4 * C5_CORR + 16 * C5_HOT + 8 * 17 + 16 + 4 * CJ_WORDS + sizeof(C5Steal);
 static_assert(C5_GATHER_LDS % 8 == 0 && C5_PROBE_LDS <= 160 * 1024, "P3 LDS layout");
 
 __device__ inline int64_t uniform64(int64_t v) {
@@ -723,6 +762,9 @@ __device__ inline int64_t uniform64(int64_t v) {
 // broadcast — no atomics, no merge, no overflow tracking).  Pad and dead-lane
 // keys are probed like real ones and Σ_{i<64} corr_out[i]·in[i] is subtracted.
 // No counter leaves LDS; the last unit to finish writes the count (no dot).
+// Phase 2 is a loop over jobs — the unit's own out-run, then tile ranges of the
+// out-runs of published buckets, each against that bucket's image loaded into
+// this unit's LDS (C5Steal above) — with ONE inlined walk(probe) in it.
 template <int PPS, bool PROBE = false>
 __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
                                                             const int32_t *nunits,
@@ -747,6 +789,8 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
   uint32_t *hk = corr_out + C5_CORR, *hv = hk + C5_HOT, *sk = hv + C5_HOT, *sx = sk + C5_HOT;
   unsigned long long *red = (unsigned long long *)(sx + C5_HOT);
   uint32_t *nspec = (uint32_t *)(red + 17), *hotpad = nspec + 1;  // [1], [2]
+  int32_t *job = (int32_t *)(nspec + 4);                          // [CJ_WORDS]
+  C5Steal *st = (C5Steal *)(job + CJ_WORDS);
   C3Unit u;
   if constexpr (PROBE) {  // unit b: in-run b, then out-run nb + b, every tile
     u.run = ui;
@@ -777,6 +821,8 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
     }
     if (threadIdx.x < C5_CORR) corr_out[threadIdx.x] = 0;
     if (threadIdx.x < 3) nspec[threadIdx.x] = 0;  // + hotpad[0..1]
+    if (threadIdx.x < CJ_WORDS) job[threadIdx.x] = 0;
+    if (threadIdx.x == 0) *st = pr.st;
   }
   // A split run's units flush with atomic adds into bins that must start at
   // zero: the first unit of (run, slice) to start sets its claim bit and clears
@@ -803,9 +849,10 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
   const uint4 *part4 = (const uint4 *)part;
   // run-major meta_t (mstride 1) or P1's tile-major meta read in place (mstride nr)
   const uint32_t *m = meta_t + (mstride == 1 ? (int64_t)u.run * ntiles : (int64_t)u.run);
-  (void)corr_out, (void)hk, (void)hv, (void)sk, (void)sx, (void)red, (void)nspec, (void)hotpad;
+  (void)corr_out, (void)hk, (void)hv, (void)sk, (void)sx, (void)red, (void)nspec, (void)hotpad, (void)job, (void)st;
   const int64_t ut = u.t1 - u.t0;
-  const int64_t w0 = uniform64(u.t0 + ut * wave / NW), w1 = uniform64(u.t0 + ut * (wave + 1) / NW);
+  // the wave's tile range of the run being walked (mode P: set again per job)
+  int64_t w0 = uniform64(u.t0 + ut * wave / NW), w1 = uniform64(u.t0 + ut * (wave + 1) / NW);
   const uint32_t rs8 = (uint32_t)(rstride / 8);
   uint32_t padc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint32_t dead = 0;
@@ -1023,9 +1070,9 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
       }
     }
   };
-  const uint32_t pcls = 8u * (uint32_t)((w0 + lane) & 7);
-  // pad / dead-lane keys of the run just walked → its correction bins
+  // pad / dead-lane keys of the tile range just walked → its correction bins
   auto flush_corr = [&](uint32_t *cb) __attribute__((always_inline)) {
+    const uint32_t pcls = 8u * (uint32_t)((w0 + lane) & 7);
 #pragma unroll
     for (int e = 1; e < 8; ++e)
       if (padc[e]) atomicAdd(&cb[pcls + e], padc[e]);
@@ -1034,9 +1081,6 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
   walk(count);
   flush_corr(corr);
   if constexpr (PROBE) {
-#pragma unroll
-    for (int e = 1; e < 8; ++e) padc[e] = 0;
-    dead = 0;
     __syncthreads();
     // Finalise: every half is < 2^15 now and nothing adds any more, so a half
     // may use all 16 bits.  A hot key's total T (slot total + remainder − its
@@ -1096,11 +1140,68 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
       }
     }
     __syncthreads();
+    // What phase 2 reads of the bucket is final now: halves[], nspec, sk[], sx[] and the
+    // bucket's entries of the global log — the bucket's image.
+    // Publish (C5Steal): claim a slot, copy the image into it, release it.  The log
+    // entries were appended above, in front of the release.
+    uint4 *const my_image = [&]() -> uint4 * {
+      if (st->steal == C5_STEAL_OFF) return nullptr;
+      if (st->steal == C5_STEAL_HEAVY) {  // the two runs' pieces: one pass over their 4·ntiles B of meta each
+        const uint32_t *mi = meta_t + (int64_t)u.run * ntiles, *mo = mi + (int64_t)nb * ntiles;
+        uint32_t qi = 0, qo = 0;
+        for (int64_t t = threadIdx.x; t < ntiles; t += C5_BLOCK) {
+          qi += ((mi[t] >> 16) + 7) >> 3;
+          qo += ((mo[t] >> 16) + 7) >> 3;
+        }
+        qi = (uint32_t)wave_reduce_sum((unsigned long long)qi);
+        qo = (uint32_t)wave_reduce_sum((unsigned long long)qo);
+        if (lane == 0 && qi) atomicAdd(&job[CJ_PIN], (int)qi);
+        if (lane == 0 && qo) atomicAdd(&job[CJ_POUT], (int)qo);
+        __syncthreads();
+      }
+      if (threadIdx.x == 0) {
+        const bool heavy = st->steal != C5_STEAL_HEAVY || (uint32_t)job[CJ_PIN] > st->heavy_pieces ||
+                           (uint32_t)job[CJ_POUT] > st->heavy_pieces;
+        const uint32_t sl = heavy ? atomicAdd(st->slots_used, 1u) : st->nslots;
+        job[CJ_MINE] = sl < st->nslots ? (int)sl : CJ_NONE;
+      }
+      __syncthreads();
+      const int sl = job[CJ_MINE];
+      return sl < 0 ? nullptr : st->images + (int64_t)sl * (C5_IMAGE_BYTES / 16);
+    }();
+    if (my_image) {
+      const uint4 *h4 = (const uint4 *)halves;
+      for (int i = threadIdx.x; i < 2 * C2_BW / 16; i += C5_BLOCK) my_image[i] = h4[i];
+      uint32_t *hd = (uint32_t *)(my_image + 2 * C2_BW / 16);
+      const uint32_t n = *nspec;
+      if (threadIdx.x == 0) *(uint4 *)hd = make_uint4(n, (uint32_t)u.run, 0u, 0u);
+      if (threadIdx.x < n) {
+        hd[4 + threadIdx.x] = sk[threadIdx.x];
+        hd[4 + 512 + threadIdx.x] = sx[threadIdx.x];
+      }
+      // every storing wave's stores have left, then ONE agent-scope release
+      // (an L2 write-back), then the flag
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store(&st->ready[job[CJ_MINE]], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    if (threadIdx.x == 0) {
+      // an unpublished bucket is ONE static job; a published one is drawn from
+      // its cursor, by its owner as by anybody (reload: from the slot's copy)
+      job[CJ_CUR] = my_image ? job[CJ_MINE] : CJ_OWN_PENDING;
+      job[CJ_IMG] = my_image && st->steal != C5_STEAL_RELOAD ? job[CJ_MINE] : CJ_OWN;
+      job[CJ_BKT] = u.run;
+    }
+    // the image in LDS: its special keys' count and its bucket's first log key
+    uint32_t ns = 0, pbase = log_base;
     // in[key] in full (cold: the pad-bin correction below)
-    const uint32_t ns = (uint32_t)__builtin_amdgcn_readfirstlane((int)*nspec);
     auto full_in = [&](uint32_t key) -> uint32_t {
       uint32_t t = halves[key];
-      if (t == 0xFFFFu) return c5_log_sum(ovf.log, ovf.n, ovf.cap, log_base + key);
+      if (t == 0xFFFFu) return c5_log_sum(ovf.log, ovf.n, ovf.cap, pbase + key);
       for (uint32_t i = 0; i < ns; ++i) t += sk[i] == key ? sx[i] : 0u;
       return t;
     };
@@ -1112,9 +1213,8 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
     // two specials live in scalars, further ones are read from LDS per step)
     // and count · extra is added at the end.
     unsigned long long sum = 0, wsum = 0;  // per lane; per wave (uniform)
-    const uint32_t ks0 = ns > 0 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)sk[0]) : 0x10000u;
-    const uint32_t ks1 = ns > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)sk[1]) : 0x10000u;
-    uint32_t cn0 = 0, cn1 = 0;  // probes of specials 0 and 1 (uniform)
+    uint32_t ks0 = 0x10000u, ks1 = 0x10000u;  // specials 0 and 1 of the image (uniform)
+    uint32_t cn0 = 0, cn1 = 0;                // their probes in this job (uniform)
     auto probe = [&](const uint4 *v, uint32_t p0, uint32_t total) __attribute__((always_inline)) {
       uint32_t s32 = 0, mx = 0;  // 16 halves < 2^16: no overflow
       uint32_t kk[PPS][8];
@@ -1167,26 +1267,135 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
           for (int j = 0; j < PPS; ++j)
 #pragma unroll
             for (int e = 0; e < 8; ++e) key = idx == (uint32_t)(8 * j + e) ? kk[j][e] : key;
-          sum += (unsigned long long)c5_log_sum(ovf.log, ovf.n, ovf.cap, log_base + key) - 0xFFFFu;
+          sum += (unsigned long long)c5_log_sum(ovf.log, ovf.n, ovf.cap, pbase + key) - 0xFFFFu;
         }
       }
     };
-    m = meta_t + (int64_t)(nb + u.run) * ntiles;  // out-run nb + b (run-major meta)
-    wpre = w0 + lane < w1 ? m[w0 + lane] : 0u;
-    walk(probe);
-    if (lane == 0) {
-      if (ns > 0) wsum += (unsigned long long)cn0 * sx[0];
-      if (ns > 1) wsum += (unsigned long long)cn1 * sx[1];
-      sum += wsum;
-    }
-    flush_corr(corr_out);
-    __syncthreads();
-    if (threadIdx.x < C5_CORR) {  // the out-run's pad / dead-lane keys were probed too
-      const uint32_t c = corr_out[threadIdx.x];
-      if (c) {
-        sum -= (unsigned long long)c * full_in(threadIdx.x);
+    // The job loop.  A job is (bucket b′, tiles [j0, j1) of out-run nb + b′), run
+    // against the image of b′ in LDS and complete in itself: its own pad /
+    // dead-lane correction and its own special-key counts.  Wave 0 finds the
+    // next job: the unit's own static one, else the next of the cursor it drew
+    // from last, else the first ready slot with jobs left (one relaxed flag
+    // load per slot; a slot that is not ready is passed over — no unit waits
+    // for another, and every cursor add that fails retires its slot for good,
+    // so the search ends).
+    for (;;) {
+      // (laundered offset: the addresses of the mailbox, the parked arguments and
+      // the specials are loop invariants, one SGPR each if hoisted out of the job
+      // loop and live across the walk; behind z they are ONE base plus immediates)
+      int z = 0;
+      asm volatile("" : "+s"(z));
+      int32_t *const jb = job + z;
+      const C5Steal *const sb = (const C5Steal *)(jb + CJ_WORDS);
+      uint32_t *const nsp = nspec + z, *const skb = sk + z, *const sxb = sx + z;
+      if (wave == 0) {
+        const uint32_t jtl = (uint32_t)__builtin_amdgcn_readfirstlane((int)sb->job_tiles);
+        const uint32_t njobs = sb->steal ? ((uint32_t)ntiles + jtl - 1) / jtl : 0u;
+        int found = CJ_NONE;
+        uint32_t ji = 0;
+        const int cur = jb[CJ_CUR];
+        if (cur == CJ_OWN_PENDING) {
+          found = CJ_OWN;
+        } else if (sb->steal) {
+          if (cur >= 0) {
+            uint32_t c = lane == 0 ? atomicAdd(&sb->cursor[cur], 1u) : 0u;
+            c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
+            if (c < njobs) found = cur, ji = c;
+          }
+          if (found < 0) {
+            const uint32_t nsl =
+                min(__hip_atomic_load(sb->slots_used, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), sb->nslots);
+            for (uint32_t s0 = 0; s0 < nsl && found < 0; s0 += WAVE) {
+              const uint32_t sl = s0 + lane;
+              bool cand = sl < nsl;
+              if (cand) cand = __hip_atomic_load(&sb->ready[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+              if (cand) cand = __hip_atomic_load(&sb->cursor[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < njobs;
+              unsigned long long mask = __builtin_amdgcn_ballot_w64(cand);
+              while (mask && found < 0) {
+                const uint32_t sc = s0 + (uint32_t)__builtin_ctzll(mask);
+                mask &= mask - 1;
+                uint32_t c = lane == 0 ? atomicAdd(&sb->cursor[sc], 1u) : 0u;
+                c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
+                if (c < njobs) found = (int)sc, ji = c;
+              }
+            }
+          }
+        }
+        const bool need = found >= 0 && found != jb[CJ_IMG];
+        if (need) {  // the slot's flag was read set: ONE agent-scope acquire, in front of the barrier
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        if (lane == 0) {
+          jb[CJ_SLOT] = found;
+          jb[CJ_IDX] = (int)ji;
+          jb[CJ_NEED] = need;
+          jb[CJ_CUR] = found >= 0 ? found : CJ_NONE;
+          if (need) jb[CJ_IMG] = found;
+          if (found >= 0 && found != jb[CJ_MINE]) jb[CJ_NSTEAL] += 1;
+        }
+      }
+      __syncthreads();
+      const int slot = __builtin_amdgcn_readfirstlane(jb[CJ_SLOT]);
+      if (slot == CJ_NONE) break;
+      if (threadIdx.x < C5_CORR) corr_out[threadIdx.x] = 0;
+      if (__builtin_amdgcn_readfirstlane(jb[CJ_NEED])) {  // the slot's image replaces the one in LDS (plain 16-B loads behind the acquire)
+        const uint4 *img = sb->images + (int64_t)slot * (C5_IMAGE_BYTES / 16);
+        uint4 *h4 = (uint4 *)halves;
+        // (laundered: the copy's addresses are loop invariants, and hoisted out of
+        // the job loop they would sit in registers across the walk — scratch)
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        for (int i = tid; i < 2 * C2_BW / 16; i += C5_BLOCK) h4[i] = img[i];
+        const uint32_t *hd = (const uint32_t *)(img + 2 * C2_BW / 16);
+        const uint32_t n = min(hd[0], (uint32_t)C5_HOT);
+        if (tid == 0) {
+          *nsp = n;
+          jb[CJ_BKT] = (int)hd[1];
+        }
+        if ((uint32_t)tid < n) {
+          skb[tid] = hd[4 + tid];
+          sxb[tid] = hd[4 + 512 + tid];
+        }
+      }
+      __syncthreads();
+      {
+        const int bkt = __builtin_amdgcn_readfirstlane(jb[CJ_BKT]);
+        // (mode P: every run's tiles are [0, ntiles))
+        const int64_t j0 = slot == CJ_OWN ? 0 : (int64_t)jb[CJ_IDX] * sb->job_tiles;
+        const int64_t jt = slot == CJ_OWN ? ntiles : min<int64_t>(sb->job_tiles, ntiles - j0);
+        w0 = uniform64(j0 + jt * wave / NW);
+        w1 = uniform64(j0 + jt * (wave + 1) / NW);
+        m = meta_t + (int64_t)(nb + bkt) * ntiles;  // out-run nb + b′ (run-major meta)
+        pbase = (uint32_t)bkt << C2_BITS;
+        ns = (uint32_t)__builtin_amdgcn_readfirstlane((int)*nsp);
+        ks0 = ns > 0 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)skb[0]) : 0x10000u;
+        ks1 = ns > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)skb[1]) : 0x10000u;
+        cn0 = cn1 = 0;
+        wsum = 0;
+#pragma unroll
+        for (int e = 1; e < 8; ++e) padc[e] = 0;
+        dead = 0;
+      }
+      wpre = w0 + lane < w1 ? m[w0 + lane] : 0u;
+      walk(probe);
+      asm volatile("" : "+s"(z));
+      const uint32_t *const sxe = sx + z;
+      if (lane == 0) {
+        if (ns > 0) wsum += (unsigned long long)cn0 * sxe[0];
+        if (ns > 1) wsum += (unsigned long long)cn1 * sxe[1];
+        sum += wsum;
+      }
+      flush_corr(corr_out);
+      __syncthreads();
+      if (threadIdx.x < C5_CORR) {  // the job's pad / dead-lane keys were probed too
+        const uint32_t c = corr_out[threadIdx.x];
+        if (c) {
+          sum -= (unsigned long long)c * full_in(threadIdx.x);
+        }
       }
     }
+    if (threadIdx.x == 0 && job[CJ_NSTEAL]) atomicAdd(st->steals, (uint32_t)job[CJ_NSTEAL]);
     // Epilogue (as k_chain2_dot_pairs): Σ and this unit's share of the
     // self-loops, then the last unit to finish writes the count
     const unsigned long long tot = block_reduce_sum(sum, red);
@@ -1270,7 +1479,8 @@ static void launch_c5(Session *s, const C5Cols<W> &c, uint16_t *part, uint32_t *
 // a C5PostPlan, built by c5_plan_fused or c5_plan_sharded and by nothing else.
 
 // Work area of the post-P1 kernels: run_total[nr] (uint64) | counters (4 ×
-// int32: [0] units, [1] hand-off events) | hand-off log | split[nr] | units.
+// int32: [0] units, [1] hand-off events, [2] image slots claimed, [3] steals) |
+// hand-off log | split[nr] | ready[slots], cursor[slots] | units | images.
 // Byte offsets; the first `zero_bytes` must start at zero — the run totals and
 // counters are added to, a reserved log slot may be read before its owner
 // wrote it (a zero entry adds nothing), and the split flags are read by the
@@ -1279,9 +1489,14 @@ struct C5PostLayout {
   int max_units;     // capacity of the work list (whole XCD waves)
   uint32_t ovf_cap;  // capacity of the hand-off log
   int64_t run_total, counters, log, split, units, bytes, zero_bytes;
+  // mode P with work sharing: counters [2] slots claimed, [3] steals; the slots'
+  // ready flags and job cursors (zeroed) in front of the units; the images (never
+  // cleared: a slot is read only behind its ready flag) at the end
+  int steal_slots;
+  int64_t steal_ctl, images;
 };
 
-static C5PostLayout c5_post_layout(int nr, int S, int split_x16, int64_t nkeys) {
+static C5PostLayout c5_post_layout(int nr, int S, int split_x16, int64_t nkeys, int steal_slots = 0) {
   C5PostLayout l;
   // runs × slices + hub splits (≤ 2 per run beyond the slices), whole XCD waves
   // Σ_runs max(S, ⌈cnt/target⌉) ≤ S·nr + nr + total/target, target ≥ split/16 × mean
@@ -1292,8 +1507,11 @@ static C5PostLayout c5_post_layout(int nr, int S, int split_x16, int64_t nkeys) 
   l.counters = l.run_total + 8 * (int64_t)nr;
   l.log = l.counters + 16;
   l.split = l.log + 8 * (int64_t)l.ovf_cap;
-  l.units = l.split + 4 * (int64_t)nr;  // nr = 2·nb is even: 8-B aligned like the log
-  l.bytes = l.units + (int64_t)sizeof(C3Unit) * l.max_units;
+  l.steal_slots = steal_slots;
+  l.steal_ctl = l.split + 4 * (int64_t)nr;  // nr = 2·nb is even: 8-B aligned like the log
+  l.units = l.steal_ctl + 8 * (int64_t)steal_slots;
+  l.images = (l.units + (int64_t)sizeof(C3Unit) * l.max_units + 15) & ~int64_t(15);
+  l.bytes = l.images + (int64_t)C5_IMAGE_BYTES * steal_slots;
   l.zero_bytes = l.units;
   assert(l.log % 8 == 0 && l.units % 8 == 0);  // uint2 entries, C3Unit's int64 fields
   return l;
@@ -1332,6 +1550,8 @@ struct C5PostPlan {
   bool zeroed_by_p1;  // P1's workgroups clear the layout's zero prefix (else: a memset here)
   C5PostLayout layout;
   uint32_t hotcap = C5_HOT;  // mode P: hot-table slots
+  // mode P: phase 2 shared between units (C5_STEAL_*; the slots are in the layout)
+  uint32_t steal = C5_STEAL_OFF, job_tiles = 0, heavy_pieces = 0;
   bool probe() const { return mode.counters == C5Counters::Probed; }
 };
 
@@ -1403,6 +1623,26 @@ static C5PostPlan c5_plan_fused(int nb, int64_t ntiles, int64_t rstride, int64_t
   C5PostPlan p = c5_plan(m, nb, ntiles, 0, ntiles, rstride, nkeys, true);
   const char *hc = getenv("CAPF_C5_HOTCAP");
   if (hc) p.hotcap = (uint32_t)std::min(C5_HOT, std::max(1, atoi(hc)));
+  if (p.probe()) {
+    // Phase 2 shared between units, on wherever mode P is.  CAPF_C5_STEAL: 0 =
+    // off (every unit probes its own out-run and nothing else), all = every
+    // unit publishes, reload (tests) = every unit publishes and re-reads its
+    // own image; unset = heavy units publish: those holding more than
+    // (1 + CAPF_C5_STEAL_THETA) × the mean pieces (keys + ~3.5 pad keys per tile,
+    // in eights) in their in-run or out-run.  CAPF_C5_STEAL_TILES: tiles per job.
+    const char *se = getenv("CAPF_C5_STEAL"), *te = getenv("CAPF_C5_STEAL_TILES"), *th = getenv("CAPF_C5_STEAL_THETA");
+    p.steal = !se                    ? C5_STEAL_HEAVY
+              : !strcmp(se, "all")    ? C5_STEAL_ALL
+              : !strcmp(se, "reload") ? C5_STEAL_RELOAD
+              : atoi(se) != 0         ? C5_STEAL_HEAVY
+                                      : C5_STEAL_OFF;
+    p.job_tiles = (uint32_t)std::max(1, te ? atoi(te) : 512);
+    const double mean = ((double)nkeys / 2 / nb + 3.5 * (double)ntiles) / 8;
+    // (floor: a run of under 2^16 keys is probed in less time than its image takes to publish)
+    p.heavy_pieces = (uint32_t)std::min(4.0e9, std::max(8192.0, (1.0 + (th ? atof(th) : 0.15)) * mean));
+    const int slots = p.steal == C5_STEAL_OFF ? 0 : p.steal == C5_STEAL_HEAVY ? C5_HEAVY_SLOTS : nb;
+    p.layout = c5_post_layout(2 * nb, p.S, p.sides.split_x16, nkeys, slots);
+  }
   return p;
 }
 
@@ -1473,7 +1713,11 @@ static C5PostOut c5_post(Session *s, const C5PostBufs &b, const C5PostPlan &p) {
     // 0.44 + 0.027 ms + a ~10 µs boundary: the dot kernel runs after P3)
     KernelTimer kt(s, "c5_gather", 2.0 * p.nkeys);
     const int grid = listed ? l.max_units : ((p.probe() ? p.sides.nb : nr * p.S) + 255) / 256 * 256;
-    const C5Probe pr{b.acc3, b.fin, b.tile_loops, p.hotcap};
+    uint32_t *sctl = (uint32_t *)(base + l.steal_ctl);
+    assert(!p.probe() || (p.sides.t0[0] == 0 && p.sides.t1[0] == p.ntiles));  // mode P's jobs cut [0, ntiles)
+    const C5Probe pr{b.acc3, b.fin, b.tile_loops, p.hotcap,
+                     C5Steal{p.steal, p.job_tiles, (uint32_t)l.steal_slots, p.heavy_pieces, (uint32_t *)(nunits + 2),
+                             (uint32_t *)(nunits + 3), sctl, sctl + l.steal_slots, (uint4 *)(base + l.images)}};
     auto kern = p.probe() ? k_c5_gather<C5_PPS, true> : k_c5_gather<C5_PPS, false>;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C5_BLOCK), p.probe() ? C5_PROBE_LDS : C5_GATHER_LDS, s->stream,
                        listed ? (const C3Unit *)units : nullptr, (const int32_t *)nunits, b.part,
@@ -1650,6 +1894,7 @@ static void chain2_c5(Session *s, C5Cols<W> c, bool in_range, uint32_t *h_in, ui
     spill->log = out.ovf.log;
     spill->n = out.ovf.n;
     spill->cap = out.ovf.cap;
+    spill->steals = out.ovf.n + 2;  // counters [3]
     spill->fin_written = true;
   }
   if (plan.S > 1) {
