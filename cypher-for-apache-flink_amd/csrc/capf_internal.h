@@ -175,7 +175,8 @@ enum Op : int32_t {
   OP_DEGREES = CAPF_OP_DEGREES, OP_RADIANS = CAPF_OP_RADIANS, OP_ATAN2 = CAPF_OP_ATAN2,
   OP_TO_BOOLEAN = CAPF_OP_TO_BOOLEAN, OP_IN_SET = CAPF_OP_IN_SET, OP_STR_MAP = CAPF_OP_STR_MAP,
   OP_VALUE_MAP = CAPF_OP_VALUE_MAP, OP_STR_TO_NUM = CAPF_OP_STR_TO_NUM, OP_RAND = CAPF_OP_RAND,
-  OP_LIST_INDEX = CAPF_OP_LIST_INDEX, OP_STR_RANK = CAPF_OP_STR_RANK
+  OP_LIST_INDEX = CAPF_OP_LIST_INDEX, OP_STR_RANK = CAPF_OP_STR_RANK,
+  OP_STR_MATCH = CAPF_OP_STR_MATCH
 };
 // a program name that refers to a session literal set ("\x01set:<id>"), not a column
 inline bool is_literal_set_name(const std::string &nm) { return nm.size() > 5 && nm.compare(0, 5, "\x01set:") == 0; }
@@ -409,6 +410,23 @@ struct Session {
   // device table of the strings as numbers (CAPF_OP_STR_TO_NUM)
   BufPtr d_str_num;
   size_t d_str_num_n = 0;
+  // device string heap (CAPF_OP_STR_MATCH): int64 offsets [n + 1] and the
+  // strings' bytes back to back, appended to as the dictionary grows
+  // (capacities in offsets / bytes, geometric)
+  BufPtr d_heap_off, d_heap_bytes;
+  size_t d_heap_n = 0, d_heap_off_cap = 0;
+  int64_t d_heap_nbytes = 0, d_heap_bytes_cap = 0;
+  // device tables of CAPF_OP_STR_MATCH with a literal pattern: one uint8
+  // (0 / 1) per dictionary code, per (kind, pattern code); oldest first, at
+  // most STR_MATCH_TABLES kept
+  struct StrMatchTable {
+    int32_t kind;
+    int64_t pattern;
+    BufPtr buf;
+    size_t n, cap;  // codes covered, capacity
+  };
+  std::mutex match_mu;
+  std::vector<StrMatchTable> match_tables;
   // small device scratch for scalar results
   int64_t *d_scalars = nullptr;  // 64 slots
   int64_t *h_scalars = nullptr;  // pinned mirror
@@ -580,6 +598,25 @@ ColPtr ranks_to_codes(Session *s, const ColPtr &ranks);
 // Device table of the session's strings parsed as numbers (CAPF_OP_STR_TO_NUM):
 // [double n][int64 n][uint8 flags n] (bit 0: a DOUBLE, bit 1: an INTEGER).
 const void *string_num_table(Session *s, size_t *n);
+// The session's strings on the device (CAPF_OP_STR_MATCH): int64 offsets
+// [n + 1] and the UTF-8 / WTF-8 bytes back to back, no terminators.  Only the
+// strings interned since the last call are uploaded.  The bytes buffer is
+// padded so that aligned 4-byte words covering any string may be read.
+struct StringHeap {
+  BufPtr off, bytes;
+  int64_t nbytes;
+};
+StringHeap string_heap(Session *s, size_t *n);
+// Device uint8 table (0 false, 1 true) of `subject <kind> pattern` per
+// dictionary code for one pattern (strings.hip); cached per (kind, pattern)
+// and extended over the codes interned since.  kind: 0 STARTS WITH, 1 ENDS
+// WITH, 2 CONTAINS.
+constexpr size_t STR_MATCH_TABLES = 16;  // cached tables per session
+BufPtr string_match_table(Session *s, int kind, int64_t pattern_code, size_t *n);
+// The path of a literal pattern over `nrows` rows: true = the table above
+// (the strings it does not cover yet are at most the rows), false = row by
+// row.  CAPF_STR_MATCH=rows|dict forces one.
+bool string_match_by_table(Session *s, int kind, int64_t pattern_code, int64_t nrows);
 // Record an error for capf_last_error() (used by entry points outside runtime.cpp).
 int32_t record_error(int32_t code, const char *msg);
 

@@ -10,6 +10,7 @@
 
 #include "capf_internal.h"
 #include "device_common.h"
+#include "str_match.h"
 
 namespace capf {
 
@@ -1229,6 +1230,26 @@ __device__ Val run_program(const Instr *code, int ncode, const ColView *cols, in
         }
         break;
       }
+      case OP_STR_MATCH: {
+        // i = 4 · view + kind.  f != 0 (a literal pattern, dictionary path):
+        // cols[view] = the pattern's answers by subject code; else cols[view],
+        // cols[view + 1] = the string heap's offsets and bytes.  base = the
+        // codes covered.
+        Val b = st[--sp], a = st[--sp];
+        const ColView &v = cols[in.i >> 2];
+        if (a.nul || b.nul || a.b < 0 || a.b >= v.base || b.b < 0 || b.b >= v.base) {
+          st[sp++] = mknull(CAPF_TYPE_BOOL);
+        } else if (in.f != 0.0) {
+          st[sp++] = mkb(((const uint8_t *)v.data)[a.b] != 0);
+        } else {
+          const int64_t *off = (const int64_t *)v.data;
+          const uint8_t *bytes = (const uint8_t *)cols[(in.i >> 2) + 1].data;
+          const int64_t q = off[a.b], poff = off[b.b];
+          const PatRef p{nullptr, poff, off[b.b + 1] - poff};
+          st[sp++] = mkb(str_match((int)(in.i & 3), bytes, q, off[a.b + 1] - q, p));
+        }
+        break;
+      }
       default: st[sp++] = mknull(CAPF_TYPE_NULL); break;
     }
   }
@@ -1387,6 +1408,40 @@ static DeviceProgram upload_program(Session *s, const Program &p,
         if (x.op == OP_TO_BOOLEAN) x.i = in.i;
       break;
     }
+  // STARTS WITH / ENDS WITH / CONTAINS: a literal pattern (the instruction
+  // before is its LIT_STRING) reads its per-dictionary-code table as one more
+  // view when that examines no more strings than the input has rows
+  // (string_match_by_table); otherwise — a column pattern too — the op reads
+  // the string heap through two views, offsets and bytes, shared by all such
+  // ops of the program.  i becomes 4 · view + kind, f the path.
+  int64_t heap_view = -1;
+  for (size_t k = 0; k < code.size(); ++k) {
+    Instr &in = code[k];
+    if (in.op != OP_STR_MATCH) continue;
+    const int64_t kind = in.i;
+    if (kind < 0 || kind > 2) illegal("string predicate kind out of range");
+    const bool lit = k > 0 && code[k - 1].op == OP_LIT_STRING;
+    if (lit && string_match_by_table(s, (int)kind, code[k - 1].i, d.nrows)) {
+      size_t nstr = 0;
+      BufPtr t = string_match_table(s, (int)kind, code[k - 1].i, &nstr);
+      in.i = 4 * (int64_t)views.size() + kind;
+      in.f = 1.0;
+      views.push_back(ColView{t->p, nullptr, (int32_t)Type::Bool, ENC_PLAIN, (int64_t)nstr});
+      dp.keep.push_back(t);
+      continue;
+    }
+    if (heap_view < 0) {
+      size_t nstr = 0;
+      const StringHeap h = string_heap(s, &nstr);
+      heap_view = (int64_t)views.size();
+      views.push_back(ColView{h.off->p, nullptr, (int32_t)Type::Int64, ENC_PLAIN, (int64_t)nstr});
+      views.push_back(ColView{h.bytes->p, nullptr, (int32_t)Type::Int64, ENC_PLAIN, h.nbytes});
+      dp.keep.push_back(h.off);
+      dp.keep.push_back(h.bytes);
+    }
+    in.i = 4 * heap_view + kind;
+    in.f = 0.0;
+  }
   dp.ncode = (int)code.size();
   dp.ncols = (int)views.size();
   // stack depth check (host) — the device stack is fixed size
@@ -1400,6 +1455,7 @@ static DeviceProgram upload_program(Session *s, const Program &p,
       case OP_TO_INTEGER: case OP_STR_LEN: case OP_TO_BOOLEAN: case OP_IN_SET: case OP_STR_MAP:
       case OP_STR_TO_NUM: case OP_LIST_INDEX: case OP_STR_RANK: break;
       case OP_IF: depth -= 2; break;
+      case OP_STR_MATCH: depth -= 1; break;  // pattern and subject in, a BOOLEAN out
       case OP_VALUE_MAP: depth -= in.f != 0.0 ? 1 : 0; break;
       default:
         if (!is_math1(in.op)) depth -= 1;  // binary operators; unary math keeps the depth

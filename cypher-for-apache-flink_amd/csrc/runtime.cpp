@@ -327,6 +327,14 @@ Type infer_type(const Program &p, const std::vector<std::string> &names,
         st.push_back(Type::Int64);
         break;
       }
+      case OP_STR_MATCH: {
+        if (in.i < 0 || in.i > 2) illegal("string predicate kind out of range");
+        Type b = pop(), a = pop();
+        if ((a != Type::String && a != Type::Null) || (b != Type::String && b != Type::Null))
+          illegal("STARTS WITH / ENDS WITH / CONTAINS of a non-string value");
+        st.push_back(Type::Bool);
+        break;
+      }
       case OP_VALUE_MAP: {
         if (in.i < 0 || (size_t)in.i >= p.names.size() || !is_value_map_name(p.names[in.i]))
           illegal("malformed expression program (value map)");
@@ -892,6 +900,57 @@ const int64_t *string_order_table(Session *s, size_t *n) {
   string_rank_table(s, n);
   std::lock_guard<std::mutex> lk(s->str_mu);
   return (const int64_t *)s->d_str_order->p;
+}
+
+// Heap buffers keep HEAP_PAD bytes past the last string: the matching kernels
+// read the aligned 4-byte words that cover a string, and CONTAINS's window one
+// word ahead.
+constexpr int64_t HEAP_PAD = 16;
+
+StringHeap string_heap(Session *s, size_t *n) {
+  std::lock_guard<std::mutex> lk(s->str_mu);
+  const size_t m = s->strings.size(), have = s->d_heap_off ? s->d_heap_n : 0;
+  if (m > have || !s->d_heap_off) {
+    // the new strings' offsets (and offset 0 the first time) and bytes
+    std::vector<int64_t> off;
+    std::string bytes;
+    if (!s->d_heap_off) off.push_back(0);
+    int64_t end = s->d_heap_off ? s->d_heap_nbytes : 0;
+    for (size_t i = have; i < m; ++i) {
+      bytes += s->strings[i];
+      end += (int64_t)s->strings[i].size();
+      off.push_back(end);
+    }
+    // geometric capacities; a grown buffer takes its content device to device
+    if (m + 1 > s->d_heap_off_cap) {
+      const size_t cap = std::max<size_t>(2 * s->d_heap_off_cap, std::max<size_t>(m + 1, 1024));
+      BufPtr nb = s->alloc(8 * cap);
+      if (s->d_heap_off)
+        HIP_CHECK(hipMemcpyAsync(nb->p, s->d_heap_off->p, 8 * (have + 1), hipMemcpyDeviceToDevice, s->stream));
+      s->d_heap_off = nb;
+      s->d_heap_off_cap = cap;
+    }
+    if (end + HEAP_PAD > s->d_heap_bytes_cap || !s->d_heap_bytes) {
+      const int64_t cap = std::max<int64_t>(2 * s->d_heap_bytes_cap, std::max<int64_t>(end + HEAP_PAD, 1 << 16));
+      BufPtr nb = s->alloc((size_t)cap);
+      if (s->d_heap_bytes && s->d_heap_nbytes > 0)
+        HIP_CHECK(hipMemcpyAsync(nb->p, s->d_heap_bytes->p, (size_t)s->d_heap_nbytes, hipMemcpyDeviceToDevice,
+                                 s->stream));
+      s->d_heap_bytes = nb;
+      s->d_heap_bytes_cap = cap;
+    }
+    const size_t first = m + 1 - off.size();  // index of the first offset uploaded
+    HIP_CHECK(hipMemcpyAsync((int64_t *)s->d_heap_off->p + first, off.data(), 8 * off.size(), hipMemcpyHostToDevice,
+                             s->stream));
+    if (!bytes.empty())
+      HIP_CHECK(hipMemcpyAsync((uint8_t *)s->d_heap_bytes->p + (end - (int64_t)bytes.size()), bytes.data(),
+                               bytes.size(), hipMemcpyHostToDevice, s->stream));
+    s->sync();  // the pageable sources
+    s->d_heap_n = m;
+    s->d_heap_nbytes = end;
+  }
+  *n = s->d_heap_n;
+  return StringHeap{s->d_heap_off, s->d_heap_bytes, s->d_heap_nbytes};
 }
 
 const void *string_num_table(Session *s, size_t *n) {

@@ -39,7 +39,7 @@ OP_STR_LEN, OP_LIST_SIZE, OP_IF = 60, 61, 62
 OP_ROUND, OP_ABS, OP_CEIL, OP_FLOOR, OP_SIGN, OP_SQRT, OP_LOG, OP_LOG10, OP_EXP = 70, 71, 72, 73, 74, 75, 76, 77, 78
 OP_SIN, OP_COS, OP_TAN, OP_ASIN, OP_ACOS, OP_ATAN, OP_DEGREES, OP_RADIANS = 79, 80, 81, 82, 83, 84, 85, 86
 OP_ATAN2, OP_TO_BOOLEAN, OP_IN_SET, OP_STR_MAP, OP_VALUE_MAP = 87, 88, 89, 90, 91
-OP_STR_TO_NUM, OP_RAND, OP_LIST_INDEX, OP_STR_RANK = 92, 93, 94, 95
+OP_STR_TO_NUM, OP_RAND, OP_LIST_INDEX, OP_STR_RANK, OP_STR_MATCH = 92, 93, 94, 95, 96
 IN_SET_MIN = 17  # list length from which IN runs as a session-set lookup (shorter: an OR of equalities)
 
 # aggregators
@@ -187,6 +187,12 @@ Modulo = _binary("Modulo", "%")
 # backend evaluates the predicate the reference expectations pin
 # (ExpressionTests.scala:246-312, NullTests.scala:93).
 RegexMatch = _binary("RegexMatch", "=~")
+# lhs STARTS WITH / ENDS WITH / CONTAINS rhs (okapi Expr.scala:370-378; Flink's
+# mapper raises NotImplemented, FlinkSQLExprMapper.scala:96-98): matched on
+# the device over the session's string heap (CAPF_OP_STR_MATCH)
+StartsWith = _binary("StartsWith", "STARTS WITH")
+EndsWith = _binary("EndsWith", "ENDS WITH")
+Contains = _binary("Contains", "CONTAINS")
 
 
 def _unary(name, fmt):
@@ -644,6 +650,9 @@ _BIN_OPS = {
     "Divide": OP_DIV, "Modulo": OP_MOD,
 }
 _ORDERED = ("LessThan", "LessThanOrEqual", "GreaterThan", "GreaterThanOrEqual")
+# CAPF_OP_STR_MATCH kinds, and the predicate over two host strings (the fold of two literals)
+_STR_MATCH = {"StartsWith": (0, str.startswith), "EndsWith": (1, str.endswith),
+              "Contains": (2, lambda s, p: p in s)}
 _CMP_NAMES = ("Equals",) + _ORDERED
 _UN_OPS = {"Not": OP_NOT, "IsNull": OP_IS_NULL, "IsNotNull": OP_IS_NOT_NULL, "ToFloat": OP_TO_FLOAT,
            "ToInteger": OP_TO_INTEGER, "Negate": OP_NEG, "Exists": OP_IS_NOT_NULL,
@@ -970,7 +979,7 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
             return T_NULL
         if isinstance(e, (ToInteger, Size, Id)):
             return T_INT
-        if isinstance(e, ToBoolean) or type(e).__name__ == "RegexMatch":
+        if isinstance(e, ToBoolean) or type(e).__name__ == "RegexMatch" or type(e).__name__ in _STR_MATCH:
             return T_BOOL
         if type(e).__name__ in _STR_FUNCS or isinstance(e, (Substring, Replace, ToString)):
             return T_STRING
@@ -1200,6 +1209,24 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
             go(e.lhs)
             emit(OP_VALUE_MAP, name_of(vmap(("regex", pat), (e.lhs,))), 0.0)
             emit(OP_TO_BOOLEAN)
+        elif cls in _STR_MATCH:
+            # two literals fold here; a NULL literal or an operand known not to
+            # be a STRING gives NULL (Cypher's answer, as for the ordering of
+            # incomparable types below); everything else is matched on the
+            # device: subject, pattern, CAPF_OP_STR_MATCH (a literal pattern is
+            # interned like any StringLit)
+            kind, fn = _STR_MATCH[cls]
+            (la, va), (lb, vb) = literal_value(e.lhs), literal_value(e.rhs)
+            ta, tb = static_type(e.lhs), static_type(e.rhs)
+            if (la and va is None) or (lb and vb is None) or \
+                    any(t is not None and t != T_STRING for t in (ta, tb)):
+                emit(OP_LIT_NULL, T_BOOL)
+            elif la and lb:
+                emit(OP_LIT_BOOL, 1 if fn(va, vb) else 0)
+            else:
+                go(e.lhs)
+                go(e.rhs)
+                emit(OP_STR_MATCH, kind)
         elif cls in _ORDERED:
             # FlinkSQLExprMapper.scala:91-94.  STRINGs order by their rank in
             # the session dictionary (CAPF_OP_STR_RANK, String.compareTo);

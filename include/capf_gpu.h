@@ -231,7 +231,17 @@ enum {
    * STRING; pushes its INTEGER rank among the session's strings in UTF-16
    * code-unit order, so <, <=, >, >= and sorting on ranks order the strings.
    * NULL in, NULL out.  capf_table_order_by applies it to a STRING key itself. */
-  CAPF_OP_STR_RANK = 95
+  CAPF_OP_STR_RANK = 95,
+  /* STARTS WITH / ENDS WITH / CONTAINS (okapi Expr.scala:369-379; Flink's
+   * mapper raises NotImplemented for the three, FlinkSQLExprMapper.scala:
+   * 96-98): pops the pattern, then the subject (both STRING); pushes a
+   * BOOLEAN.  iarg is the kind: 0 STARTS WITH, 1 ENDS WITH, 2 CONTAINS.  A
+   * NULL operand gives NULL.  Matching is on the strings' UTF-8 bytes in the
+   * session's device string heap (equal to matching code points); an empty
+   * pattern matches every subject.  A literal pattern is answered from a
+   * device table per dictionary string when that examines no more strings
+   * than the input has rows, else row by row.                               */
+  CAPF_OP_STR_MATCH = 96
 };
 
 typedef struct capf_expr {

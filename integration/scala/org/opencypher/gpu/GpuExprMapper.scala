@@ -43,7 +43,12 @@ object GpuExprMapper {
   // round 6: string → number casts, rand(), xs[i] on LIST columns
   private final val StrToNum = 92; private final val Rand_ = 93; private final val ListIndex = 94
   private final val StrRank = 95  // a STRING's rank in String.compareTo order (ordered comparisons)
-  private final val InSetMin = 17  // IN lists from this length: one set lookup per row (expr.py IN_SET_MIN)
+  // STARTS WITH / ENDS WITH / CONTAINS on the device string heap; iarg = the kind
+  private final val StrMatch = Native.OpStrMatch
+  private final val StartsWithKind = Native.StrMatchStartsWith.toLong
+  private final val EndsWithKind = Native.StrMatchEndsWith.toLong
+  private final val ContainsKind = Native.StrMatchContains.toLong
+  private final val InSetMin = 17 // IN lists from this length: one set lookup per row (expr.py IN_SET_MIN)
 
   def program(expr: Expr, header: RecordHeader, table: GpuTable, parameters: CypherMap): Program = {
     val ops = mutable.ArrayBuffer.empty[Int]
@@ -175,6 +180,25 @@ object GpuExprMapper {
       }
     }
 
+    // STARTS WITH / ENDS WITH / CONTAINS (Expr.scala:369-379; FlinkSQLExprMapper.scala:96-98
+    // raises NotImplemented): two literals fold, a NULL literal or an operand known
+    // not to be a STRING gives NULL, everything else is subject, pattern,
+    // CAPF_OP_STR_MATCH (expr.py's _STR_MATCH lowering)
+    def strMatch(l: Expr, r: Expr, kind: Long): Unit = {
+      val known = Set[CypherType](CTInteger, CTFloat, CTBoolean, CTNull, CTVoid)
+      (literal(l), literal(r)) match {
+        case (Some(CypherNull), _) | (_, Some(CypherNull)) => emit(LitNull, Native.TypeBool)
+        case _ if known(l.cypherType.material) || known(r.cypherType.material) => emit(LitNull, Native.TypeBool)
+        case (Some(CypherString(s)), Some(CypherString(p))) =>
+          emit(LitBool, if (kind == StartsWithKind) { if (s.startsWith(p)) 1L else 0L }
+                        else if (kind == EndsWithKind) { if (s.endsWith(p)) 1L else 0L }
+                        else { if (s.contains(p)) 1L else 0L })
+        case (Some(a), Some(b)) if !a.isInstanceOf[CypherString] || !b.isInstanceOf[CypherString] =>
+          emit(LitNull, Native.TypeBool)
+        case _ => go(l); go(r); emit(StrMatch, kind)
+      }
+    }
+
     def go(e: Expr): Unit = e match {
       case _: Var | _: HasLabel | _: HasType | _: StartNode | _: EndNode | _: ElementProperty =>
         physical(e) match {
@@ -211,7 +235,11 @@ object GpuExprMapper {
       case ToFloat(x) => go(x); emit(ToFloat_)
       case ToInteger(x) => go(x); emit(ToInteger_)                          // Flink: INT (FlinkSQLExprMapper.scala:183)
       case Rand => emit(Rand_, scala.util.Random.nextLong() >>> 1)          // :207, a fresh seed per program
-      case RegexMatch(l, r) =>                                             // :99 — the predicate, not regexpExtract
+      // :96-98: NotImplemented in Flink (matched by type: lhs / rhs are the case classes' fields, Expr.scala:369-379)
+      case p: StartsWith => strMatch(p.lhs, p.rhs, StartsWithKind)
+      case p: EndsWith => strMatch(p.lhs, p.rhs, EndsWithKind)
+      case p: Contains => strMatch(p.lhs, p.rhs, ContainsKind)
+      case RegexMatch(l, r) =>                                           // :99 — the predicate, not regexpExtract
         literal(r) match {
           case Some(CypherNull) => emit(LitNull, Native.TypeBool)
           // the match of each distinct subject value of this table (not of the

@@ -58,6 +58,12 @@ object Native {
   final val AggPercentileCont = 9   // PercentileUdafs.scala:83-96 (Spark backend semantics)
   final val AggPercentileDisc = 10  // PercentileUdafs.scala:59-81
 
+  // CAPF_OP_STR_MATCH (opcode 96) and its kinds (the instruction's iarg)
+  final val OpStrMatch = 96
+  final val StrMatchStartsWith = 0
+  final val StrMatchEndsWith = 1
+  final val StrMatchContains = 2
+
   /** Runs a native call, rethrowing its failure as the okapi exception of that kind
     * (okapi-api/.../impl/exception/InternalException.scala:36-65). */
   def guard[A](body: => A): A =
