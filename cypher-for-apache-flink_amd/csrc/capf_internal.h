@@ -90,6 +90,7 @@ struct ColStats {
 enum : int32_t { ENC_PLAIN = 0, ENC_FOR32 = 1, ENC_FOR24 = 2 };
 
 struct Column;
+struct VrIndex;  // var_length_reach.hip
 // Late materialisation: a column defined as rows `idx` of `src` (a join side,
 // a filter, a sort), gathered only when a kernel or a download reads it
 // (force).  Gathers of gathers compose their indexes instead of moving data.
@@ -135,7 +136,7 @@ struct Column {
   // the direct-address index of a dense unique id column (dense_join.hip)
   mutable std::shared_ptr<void> dense;
   // the var-length reach index of this rel source column (var_length_reach.hip)
-  mutable std::shared_ptr<void> vr_index;
+  mutable std::shared_ptr<VrIndex> vr_index;
   // the membership bitmap of this (unique) key column over [bits_key[0],
   // bits_key[1]] (fused_count.hip message passing)
   mutable std::shared_ptr<void> bits;
@@ -623,28 +624,30 @@ int32_t record_error(int32_t code, const char *msg);
 // Fused counting over lazy inner-join trees (the Expand hot path).
 bool try_fused_count(const NodePtr &n, int64_t *out);
 // Config 5 below the SPI: Group(a; count(*)) over Distinct(a, b) over the
-// UNION ALL of the var-length join chains k = 1..u (fused_count.hip) →
+// UNION ALL of the var-length join chains k = 1..u (reach_plan.hip) →
 // the (a-keys, reach) rows by multi-source BFS; chains k = l..u with
 // 2 ≤ l ≤ u ≤ 4 and all their NOT(e_i = e_j) filters → by trail
 // enumeration; false: not that shape.
 bool try_fused_reach(const NodePtr &grp, DataPtr &out);
-// Multi-source BFS reach (var_length_reach.hip): rows (a, #targets reachable
-// by a walk of length 1..upper) for every source reaching one; include_self
-// (lower bound 0): every source, (a, a) counted once whatever its labels.
-// lower ≥ 2 (≤ upper ≤ 4): #targets joined by a trail of length lower..upper,
-// by per-source trail enumeration over an out-CSR (each row of the rel table
-// one rel); nullptr when the id dictionary exceeds the kernel's LDS bitmap
-// (2^20 nodes, CAPF_VT_MAX_NODES lowers it) — the caller runs the join chain.
+// The patterns the fused reach answers, and how (var_length_reach.hip):
+//   BFS     directed, lower 0 | 1, 1 ≤ upper ≤ 64: multi-source BFS
+//   TRAILS  directed, 2 ≤ lower ≤ upper ≤ 4: per-source trail enumeration
+//   STEPS   undirected, 0 ≤ lower ≤ upper ≤ 4: per-source enumeration of the
+//           lowering's (node, mode) steps (VarLengthExpandPlanner.scala:277-307)
+// The C entry, the plan matcher and var_length_reach_rows all ask here.
+enum class ReachMethod { NONE, BFS, TRAILS, STEPS };
+ReachMethod reach_method(bool undirected, int lower, int upper);
+// Rows (a, #targets joined to a by a path of the pattern) for every source
+// with one.  BFS: a walk of length 1..upper; lower bound 0 also pairs every
+// source with itself, once, whatever its labels.  TRAILS / STEPS: paths of
+// pairwise distinct rels (each row of the rel table one rel) of length
+// lower..upper.  One dictionary, index cache and output shape for all three;
+// nullptr outside reach_method's domain, and from the two enumerations when
+// the id dictionary exceeds the kernels' LDS bitmap (2^20 nodes,
+// CAPF_VT_MAX_NODES lowers it) — the caller runs the join chain.
 DataPtr var_length_reach_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m,
                               const ColPtr &sid, int64_t ns_in, const ColPtr &tid, int64_t nt, int lower,
-                              int upper);
-// The undirected lowering's reach (VarLengthExpandPlanner.scala:277-307), by
-// per-source enumeration of its (node, mode) steps, 0 ≤ lower ≤ upper ≤ 4:
-// same dictionary, index cache and output rows; nullptr outside those bounds
-// and above the same node limit.
-DataPtr var_length_reach_undirected_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m,
-                                         const ColPtr &sid, int64_t ns_in, const ColPtr &tid, int64_t nt,
-                                         int lower, int upper);
+                              int upper, bool undirected);
 // Radix-partitioned LDS histograms of the 2-hop count (chain2_partitioned.hip).
 // cols = {start(r1), end(r1), start(r2), end(r2)}, all plain or all FOR32.
 // Histograms hold chain2_hist_len(hi − lo + 1) counters indexed by

@@ -1663,14 +1663,13 @@ static C5PostPlan c5_plan_sharded(int nbl, int64_t t_in, int64_t ntiles, int64_t
 static C5PostOut c5_post(Session *s, const C5PostBufs &b, const C5PostPlan &p) {
   const int nr = 2 * p.sides.nb;
   const C5PostLayout &l = p.layout;
-  static bool attr_set = false;
-  if (!attr_set) {
+  static std::once_flag attr_once;  // sessions on several threads come through here
+  std::call_once(attr_once, [] {
     HIP_CHECK(hipFuncSetAttribute((const void *)k_c5_gather<C5_PPS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   C5_GATHER_LDS));
     HIP_CHECK(hipFuncSetAttribute((const void *)k_c5_gather<C5_PPS, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   C5_PROBE_LDS));
-    attr_set = true;
-  }
+  });
   char *base = (char *)b.acc->p;
   unsigned long long *run_total = (unsigned long long *)(base + l.run_total);
   int32_t *nunits = (int32_t *)(base + l.counters);

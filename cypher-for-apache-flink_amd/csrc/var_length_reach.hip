@@ -304,16 +304,41 @@ __global__ void k_vt_tmask(const uint8_t *tflag, uint32_t D, uint32_t *tmask) {
   }
 }
 
-// sources by decreasing out-degree: a hub source's workgroup starts first
-__global__ void k_vt_srckey(const int64_t *src_nodes, int64_t ns, const uint32_t *orow, uint64_t *key) {
+// sources by decreasing degree: a hub source's workgroup starts first.  The
+// degree is the out-degree, plus the in-degree where irow is given (the
+// undirected steps; out + in ≤ 2m < 2^32)
+__global__ void k_vt_srckey(const int64_t *src_nodes, int64_t ns, const uint32_t *orow, const uint32_t *irow,
+                            uint64_t *key) {
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < ns;
        j += (int64_t)gridDim.x * blockDim.x) {
     const int64_t a = src_nodes[j];
-    key[j] = ((uint64_t)(0xFFFFFFFFu - (orow[a + 1] - orow[a])) << 32) | (uint64_t)j;
+    uint32_t deg = orow[a + 1] - orow[a];
+    if (irow) deg += irow[a + 1] - irow[a];
+    key[j] = ((uint64_t)(0xFFFFFFFFu - deg) << 32) | (uint64_t)j;
   }
 }
 
 __device__ inline void vt_mark(uint32_t *bm, uint32_t y) { atomicOr(&bm[y >> 5], 1u << (y & 31)); }
+
+// Prologue of an enumeration block: zeroes its n bitmap words and the two
+// control words behind them (ctl[0] the first-hop cursor, ctl[1] the count).
+__device__ __forceinline__ void vt_clear(uint32_t *lds, uint32_t n, uint32_t *ctl) {
+  for (uint32_t w = threadIdx.x; w < n; w += VT_BLOCK) lds[w] = 0;
+  if (threadIdx.x < 2) ctl[threadIdx.x] = 0;
+  __syncthreads();
+}
+
+// Epilogue: once every wave's marks are in, reach[j] = popcount(bitmap ∧ tmask).
+__device__ __forceinline__ void vt_count(const uint32_t *bm, const uint32_t *__restrict__ tmask, uint32_t W,
+                                         uint32_t *ctl, int lane, int64_t j, int64_t *reach) {
+  __syncthreads();
+  uint32_t c = 0;
+  for (uint32_t w = threadIdx.x; w < W; w += VT_BLOCK) c += (uint32_t)__popc(bm[w] & tmask[w]);
+  c = wave_reduce_sum(c);
+  if (lane == 0 && c) atomicAdd(&ctl[1], c);
+  __syncthreads();
+  if (threadIdx.x == 0) reach[j] = (int64_t)ctl[1];
+}
 
 // The wave stands at node d_S with out-row [b, e) after a trail of S rels whose
 // positions are s1..s3 (VT_NONE beyond S) and whose start nodes are d0..d_{S-1}
@@ -417,9 +442,7 @@ __global__ __launch_bounds__(VT_BLOCK) void k_vt_trails(const uint32_t *__restri
   const uint32_t W = (D + 31) / 32, Wp = (W + 3) & ~3u;
   uint32_t *bm = vt_lds, *ex = use_ex ? vt_lds + Wp : nullptr;
   uint32_t *ctl = vt_lds + (use_ex ? 2 * Wp : Wp);
-  for (uint32_t w = threadIdx.x; w < (use_ex ? 2 * Wp : Wp); w += VT_BLOCK) vt_lds[w] = 0;
-  if (threadIdx.x < 2) ctl[threadIdx.x] = 0;
-  __syncthreads();
+  vt_clear(vt_lds, use_ex ? 2 * Wp : Wp, ctl);
   const int64_t j = (int64_t)(uint32_t)sorder[blockIdx.x];
   const uint32_t a = (uint32_t)src_nodes[j];
   const uint32_t r0 = orow[a], r1 = orow[a + 1];
@@ -442,13 +465,7 @@ __global__ __launch_bounds__(VT_BLOCK) void k_vt_trails(const uint32_t *__restri
     }
     vt_walk<1, U>(orow, ocol, bm, ex, lower, yb, ye, p, VT_NONE, VT_NONE, a, y, VT_NONE, VT_NONE, lane);
   }
-  __syncthreads();
-  uint32_t c = 0;
-  for (uint32_t w = threadIdx.x; w < W; w += VT_BLOCK) c += (uint32_t)__popc(bm[w] & tmask[w]);
-  c = wave_reduce_sum(c);
-  if (lane == 0 && c) atomicAdd(&ctl[1], c);
-  __syncthreads();
-  if (threadIdx.x == 0) reach[j] = (int64_t)ctl[1];
+  vt_count(bm, tmask, W, ctl, lane, j, reach);
 }
 
 // ------------------------------------------------------------------ undirected steps
@@ -471,32 +488,23 @@ struct VuCsr {
   const uint2 *__restrict__ iadj;
 };
 
-// records where each rel row lands in the out-CSR (k_vr_fill does not)
-__global__ void k_vu_fill_out(const uint32_t *si, const uint32_t *di, int64_t m, uint32_t *cursor,
-                              uint32_t *ocol, uint32_t *opos) {
+// The in-rows, filled from the out-CSR itself: out position p lies in the row
+// of x, the one row with orow[x] ≤ p < orow[x + 1] (binary search over the
+// D + 1 bounds, orow[0] = 0 ≤ p < m = orow[D]; empty rows on either side of x
+// share a bound with it and fail the test), and leads to y = ocol[p], so
+// (x, p) goes into y's in-row through the cursor (a copy of irow).
+__global__ void k_vu_fill_in(const uint32_t *orow, const uint32_t *ocol, uint32_t D, int64_t m, uint32_t *cursor,
+                             uint2 *iadj) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m;
        i += (int64_t)gridDim.x * blockDim.x) {
-    const uint32_t p = atomicAdd(&cursor[si[i]], 1u);
-    ocol[p] = di[i];
-    opos[i] = p;
-  }
-}
-
-__global__ void k_vu_fill_in(const uint32_t *si, const uint32_t *di, const uint32_t *opos, int64_t m,
-                             uint32_t *cursor, uint2 *iadj) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m;
-       i += (int64_t)gridDim.x * blockDim.x)
-    iadj[atomicAdd(&cursor[di[i]], 1u)] = make_uint2(si[i], opos[i]);
-}
-
-// sources by decreasing total degree (out + in ≤ 2m < 2^32)
-__global__ void k_vu_srckey(const int64_t *src_nodes, int64_t ns, const uint32_t *orow, const uint32_t *irow,
-                            uint64_t *key) {
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < ns;
-       j += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t a = src_nodes[j];
-    const uint32_t deg = (orow[a + 1] - orow[a]) + (irow[a + 1] - irow[a]);
-    key[j] = ((uint64_t)(0xFFFFFFFFu - deg) << 32) | (uint64_t)j;
+    const uint32_t p = (uint32_t)i;
+    uint32_t lo = 0, hi = D;  // orow[lo] ≤ p < orow[hi]
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + ((hi - lo) >> 1);
+      if (orow[mid] <= p) lo = mid;
+      else hi = mid;
+    }
+    iadj[atomicAdd(&cursor[ocol[p]], 1u)] = make_uint2(lo, p);
   }
 }
 
@@ -625,9 +633,7 @@ __global__ __launch_bounds__(VT_BLOCK) void k_vu_steps(const uint32_t *__restric
   extern __shared__ __attribute__((aligned(16))) uint32_t vu_lds[];
   const uint32_t W = (D + 31) / 32, Wp = (W + 3) & ~3u;
   uint32_t *bm = vu_lds, *ctl = vu_lds + Wp;
-  for (uint32_t w = threadIdx.x; w < Wp; w += VT_BLOCK) bm[w] = 0;
-  if (threadIdx.x < 2) ctl[threadIdx.x] = 0;
-  __syncthreads();
+  vt_clear(bm, Wp, ctl);
   const int64_t j = (int64_t)(uint32_t)sorder[blockIdx.x];
   const uint32_t a = (uint32_t)src_nodes[j];
   const int lane = lane_id();
@@ -654,158 +660,161 @@ __global__ __launch_bounds__(VT_BLOCK) void k_vu_steps(const uint32_t *__restric
       if constexpr (U >= 2) vu_walk<1, U>(g, bm, lower, y, nm, r, VT_NONE, VT_NONE, lane);
     }
   }
-  __syncthreads();
-  uint32_t c = 0;
-  for (uint32_t w = threadIdx.x; w < W; w += VT_BLOCK) c += (uint32_t)__popc(bm[w] & tmask[w]);
-  c = wave_reduce_sum(c);
-  if (lane == 0 && c) atomicAdd(&ctl[1], c);
-  __syncthreads();
-  if (threadIdx.x == 0) reach[j] = (int64_t)ctl[1];
+  vt_count(bm, tmask, W, ctl, lane, j, reach);
 }
 
 // HBM budget of the three MS-BFS state arrays (sources are batched to fit)
 constexpr double VR_STATE_BUDGET = 24e9;
 
+// The environment knobs, read once per query and never kept: the tests change
+// them between queries of one process.
+struct VrKnobs {
+  double budget;      // CAPF_VR_BUDGET (tests): a smaller state budget in bytes → more source batches
+  bool count_bs;      // CAPF_VR_COUNT=0 (tuning): the ballot-transpose count
+  bool expand;        // CAPF_VT_EXPAND=0 (tests, tuning): never the expanded-rows bitmap
+  int64_t max_nodes;  // CAPF_VT_MAX_NODES (tests): a lower node limit of the enumeration kernels
+};
+
+static VrKnobs vr_knobs() {
+  const char *vb = getenv("CAPF_VR_BUDGET"), *vc = getenv("CAPF_VR_COUNT");
+  const char *ve = getenv("CAPF_VT_EXPAND"), *vm = getenv("CAPF_VT_MAX_NODES");
+  VrKnobs k;
+  k.budget = vb && atof(vb) > 0 ? atof(vb) : VR_STATE_BUDGET;
+  k.count_bs = !(vc && atoi(vc) == 0);
+  k.expand = !(ve && atoi(ve) == 0);
+  k.max_nodes = vm && atoll(vm) > 0 ? std::min<int64_t>(atoll(vm), VT_MAX_NODES) : VT_MAX_NODES;
+  return k;
+}
+
 // The reach index of (rels, sources, targets): id dictionary, dense endpoint
 // indices, in-CSR by target, the degree order of its rows, source positions
 // and target flags.  Everything here is a function of four immutable columns,
 // so it is built by the first query and cached on the rel source column (an
-// ingest-time adjacency index, like the triangle's oriented CSR); a query with
-// other node columns (e.g. a filtered scan) builds its own.
+// ingest-time adjacency index, like the triangle's oriented CSR) together with
+// the other three columns and their lengths, its key; a query with other node
+// columns (e.g. a filtered scan) builds its own.
 struct VrIndex {
+  std::weak_ptr<Column> rdst, sid, tid;
+  int64_t m = 0, ns_in = 0, nt = 0;
   uint32_t D = 0;
   int64_t ns = 0;
   BufPtr dict, si, di, tflag, src_nodes, rowptr, cols, order, srcpos;
-  // the trail part (lower bound ≥ 2), built by the first trail query: out-CSR
-  // by source (a rel's identity = its position in ocol), target bitmask of
-  // ⌈D/32⌉ words, sources by decreasing out-degree
-  std::mutex vt_mu;
+  // The enumeration part (trails, undirected steps), built on first use under
+  // en_mu.  By the first enumeration query of either kind: the out-CSR by
+  // source, whose positions are the rel identities of both kernels, the target
+  // bitmask of ⌈D/32⌉ words, the sources by decreasing out-degree.  By the
+  // first undirected query, on top: in-adjacency entries (start node, out
+  // position) in the in-CSR's rows (rowptr), the sources by decreasing out + in
+  // degree.
+  std::mutex en_mu;
   BufPtr orow, ocol, tmask, sorder;
-  // the undirected part, built by the first undirected query on top of the
-  // trail part (orow, tmask) and the in-CSR's rowptr: an out-CSR filled with
-  // every rel row's position recorded, in-CSR entries (start node, out
-  // position) in rowptr's rows, sources by decreasing out + in degree
-  std::mutex vu_mu;
-  BufPtr uocol, uiadj, usorder;
+  BufPtr uiadj, usorder;
 };
 
-static void vt_build(Session *s, VrIndex &ix, int64_t m) {
-  std::lock_guard<std::mutex> lk(ix.vt_mu);
-  if (ix.orow) return;
-  const uint32_t D = ix.D;
-  const int64_t W = ((int64_t)D + 31) / 32;
+// CSR of m (row, value) pairs over D rows: degree count, exclusive scan into
+// the D + 1 row bounds, fill through a cursor copy of them.
+static void vr_csr(Session *s, const uint32_t *row, const uint32_t *val, int64_t m, uint32_t D, BufPtr &rowptr,
+                   BufPtr &cols) {
+  const size_t nb = 4 * ((size_t)D + 1);
   const unsigned g = grid_for(m, 256, 256 * 64);
-  BufPtr deg = s->alloc(4 * ((int64_t)D + 1)), orow = s->alloc(4 * ((int64_t)D + 1));
-  BufPtr cursor = s->alloc(4 * ((int64_t)D + 1)), ocol = s->alloc(4 * m), tmask = s->alloc(4 * W);
-  BufPtr skey = s->alloc(8 * ix.ns), sorder = s->alloc(8 * ix.ns);
-  HIP_CHECK(hipMemsetAsync(deg->p, 0, 4 * ((int64_t)D + 1), s->stream));
-  {
-    KernelTimer kt(s, "vt_index", 16.0 * m);
-    hipLaunchKernelGGL(k_vr_indeg, dim3(g), dim3(256), 0, s->stream, (const uint32_t *)ix.si->p, m,
-                       (uint32_t *)deg->p);
-    BufPtr tot = s->alloc(16);
-    exclusive_scan_u32_async(s, (const uint32_t *)deg->p, (uint32_t *)orow->p, (int64_t)D + 1,
-                             (uint32_t *)tot->p);
-    HIP_CHECK(hipMemcpyAsync(cursor->p, orow->p, 4 * ((int64_t)D + 1), hipMemcpyDeviceToDevice,
-                             s->stream));
-    // rows keyed by the rel's source, holding its target
-    hipLaunchKernelGGL(k_vr_fill, dim3(g), dim3(256), 0, s->stream, (const uint32_t *)ix.di->p,
-                       (const uint32_t *)ix.si->p, m, (uint32_t *)cursor->p, (uint32_t *)ocol->p);
-    hipLaunchKernelGGL(k_vt_tmask, dim3(grid_for(W, 256)), dim3(256), 0, s->stream,
-                       (const uint8_t *)ix.tflag->p, D, (uint32_t *)tmask->p);
-    hipLaunchKernelGGL(k_vt_srckey, dim3(grid_for(ix.ns, 256)), dim3(256), 0, s->stream,
-                       (const int64_t *)ix.src_nodes->p, ix.ns, (const uint32_t *)orow->p,
-                       (uint64_t *)skey->p);
-    KERNEL_CHECK();
-    vr_rocprim(s, [&](void *t, size_t &n) {
-      return rocprim::radix_sort_keys(t, n, (const uint64_t *)skey->p, (uint64_t *)sorder->p,
-                                      (size_t)ix.ns, 0, 64, s->stream);
-    });
-  }
-  s->sync();  // deg / cursor / skey are released here
-  ix.ocol = ocol;
-  ix.tmask = tmask;
-  ix.sorder = sorder;
-  ix.orow = orow;
-}
-
-// reach[j] of every source j by trail enumeration (lower ≥ 2, upper ≤ 4)
-static void vt_reach(Session *s, VrIndex &ix, int64_t m, int lower, int upper, int64_t *reach) {
-  vt_build(s, ix, m);
-  static bool attr_set = false;
-  const int max_lds = (int)VT_LDS_MAX;
-  if (!attr_set) {
-    HIP_CHECK(hipFuncSetAttribute((const void *)k_vt_trails<2>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIP_CHECK(hipFuncSetAttribute((const void *)k_vt_trails<3>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIP_CHECK(hipFuncSetAttribute((const void *)k_vt_trails<4>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    attr_set = true;
-  }
-  const uint32_t D = ix.D;
-  // the expanded-rows bitmap while two bitmaps fit the LDS (D up to about 655 k);
-  // CAPF_VT_EXPAND=0 (tests, tuning): never
-  const size_t wp = (size_t)(((D + 31) / 32 + 3) & ~3u);
-  const char *ve = getenv("CAPF_VT_EXPAND");
-  const int use_ex = !(ve && atoi(ve) == 0) && 4 * (2 * wp + 4) <= VT_LDS_MAX;
-  const size_t lds = 4 * ((use_ex ? 2 * wp : wp) + 4);
-  auto *k = upper == 2 ? k_vt_trails<2> : upper == 3 ? k_vt_trails<3> : k_vt_trails<4>;
-  KernelTimer kt(s, "vt_trails", 4.0 * m);
-  hipLaunchKernelGGL(k, dim3((unsigned)ix.ns), dim3(VT_BLOCK), lds, s->stream, (const uint32_t *)ix.orow->p,
-                     (const uint32_t *)ix.ocol->p, (const uint64_t *)ix.sorder->p,
-                     (const int64_t *)ix.src_nodes->p, (const uint32_t *)ix.tmask->p, D, lower, use_ex, reach);
+  BufPtr deg = s->alloc(nb), cursor = s->alloc(nb), tot = s->alloc(16);
+  rowptr = s->alloc(nb);
+  cols = s->alloc(4 * m);
+  HIP_CHECK(hipMemsetAsync(deg->p, 0, nb, s->stream));
+  hipLaunchKernelGGL(k_vr_indeg, dim3(g), dim3(256), 0, s->stream, row, m, (uint32_t *)deg->p);
+  exclusive_scan_u32_async(s, (const uint32_t *)deg->p, (uint32_t *)rowptr->p, (int64_t)D + 1, (uint32_t *)tot->p);
+  HIP_CHECK(hipMemcpyAsync(cursor->p, rowptr->p, nb, hipMemcpyDeviceToDevice, s->stream));
+  hipLaunchKernelGGL(k_vr_fill, dim3(g), dim3(256), 0, s->stream, val, row, m, (uint32_t *)cursor->p,
+                     (uint32_t *)cols->p);
   KERNEL_CHECK();
 }
 
-static void vu_build(Session *s, VrIndex &ix, int64_t m) {
-  vt_build(s, ix, m);
-  std::lock_guard<std::mutex> lk(ix.vu_mu);
-  if (ix.uocol) return;
-  const uint32_t D = ix.D;
-  const unsigned g = grid_for(m, 256, 256 * 64);
-  BufPtr cursor = s->alloc(4 * ((int64_t)D + 1)), uocol = s->alloc(4 * m), opos = s->alloc(4 * m);
-  BufPtr uiadj = s->alloc(8 * m), skey = s->alloc(8 * ix.ns), usorder = s->alloc(8 * ix.ns);
-  {
-    KernelTimer kt(s, "vu_index", 40.0 * m);
-    HIP_CHECK(hipMemcpyAsync(cursor->p, ix.orow->p, 4 * ((int64_t)D + 1), hipMemcpyDeviceToDevice, s->stream));
-    hipLaunchKernelGGL(k_vu_fill_out, dim3(g), dim3(256), 0, s->stream, (const uint32_t *)ix.si->p,
-                       (const uint32_t *)ix.di->p, m, (uint32_t *)cursor->p, (uint32_t *)uocol->p,
-                       (uint32_t *)opos->p);
-    HIP_CHECK(hipMemcpyAsync(cursor->p, ix.rowptr->p, 4 * ((int64_t)D + 1), hipMemcpyDeviceToDevice, s->stream));
-    hipLaunchKernelGGL(k_vu_fill_in, dim3(g), dim3(256), 0, s->stream, (const uint32_t *)ix.si->p,
-                       (const uint32_t *)ix.di->p, (const uint32_t *)opos->p, m, (uint32_t *)cursor->p,
-                       (uint2 *)uiadj->p);
-    hipLaunchKernelGGL(k_vu_srckey, dim3(grid_for(ix.ns, 256)), dim3(256), 0, s->stream,
-                       (const int64_t *)ix.src_nodes->p, ix.ns, (const uint32_t *)ix.orow->p,
-                       (const uint32_t *)ix.rowptr->p, (uint64_t *)skey->p);
-    KERNEL_CHECK();
-    vr_rocprim(s, [&](void *t, size_t &n) {
-      return rocprim::radix_sort_keys(t, n, (const uint64_t *)skey->p, (uint64_t *)usorder->p,
-                                      (size_t)ix.ns, 0, 64, s->stream);
-    });
-  }
-  s->sync();  // cursor / opos / skey are released here
-  ix.uiadj = uiadj;
-  ix.usorder = usorder;
-  ix.uocol = uocol;
+// The degree order of the sources (k_vt_srckey): keys sorted ascending, the
+// low word of each the source's position in src_nodes.
+static BufPtr vt_source_order(Session *s, const VrIndex &ix, const uint32_t *irow) {
+  BufPtr skey = s->alloc(8 * ix.ns), sorder = s->alloc(8 * ix.ns);
+  hipLaunchKernelGGL(k_vt_srckey, dim3(grid_for(ix.ns, 256)), dim3(256), 0, s->stream,
+                     (const int64_t *)ix.src_nodes->p, ix.ns, (const uint32_t *)ix.orow->p, irow,
+                     (uint64_t *)skey->p);
+  KERNEL_CHECK();
+  vr_rocprim(s, [&](void *t, size_t &n) {
+    return rocprim::radix_sort_keys(t, n, (const uint64_t *)skey->p, (uint64_t *)sorder->p, (size_t)ix.ns, 0, 64,
+                                    s->stream);
+  });
+  return sorder;
 }
 
-// reach[j] of every source j by step enumeration (undirected, 0 ≤ lower ≤ upper ≤ 4)
-static void vu_reach(Session *s, VrIndex &ix, int64_t m, int lower, int upper, int64_t *reach) {
-  vu_build(s, ix, m);
-  using Kern = void (*)(const uint32_t *, const uint32_t *, const uint32_t *, const uint2 *, const uint64_t *,
-                        const int64_t *, const uint32_t *, uint32_t, int, int64_t *);
-  static const Kern kerns[5] = {k_vu_steps<0>, k_vu_steps<1>, k_vu_steps<2>, k_vu_steps<3>, k_vu_steps<4>};
+// Builds what of the enumeration part the query needs and the index lacks.
+// Each half is synchronised before the index shows it: another session may
+// read it from its own stream.
+static void vt_build(Session *s, VrIndex &ix, bool undirected) {
+  std::lock_guard<std::mutex> lk(ix.en_mu);
+  const uint32_t D = ix.D;
+  const int64_t m = ix.m;
+  if (!ix.sorder) {
+    const int64_t W = ((int64_t)D + 31) / 32;
+    {
+      KernelTimer kt(s, "vt_index", 16.0 * m);
+      // rows keyed by the rel's source, holding its target
+      vr_csr(s, (const uint32_t *)ix.si->p, (const uint32_t *)ix.di->p, m, D, ix.orow, ix.ocol);
+      ix.tmask = s->alloc(4 * W);
+      hipLaunchKernelGGL(k_vt_tmask, dim3(grid_for(W, 256)), dim3(256), 0, s->stream,
+                         (const uint8_t *)ix.tflag->p, D, (uint32_t *)ix.tmask->p);
+      KERNEL_CHECK();
+      ix.sorder = vt_source_order(s, ix, nullptr);
+    }
+    s->sync();
+  }
+  if (undirected && !ix.usorder) {
+    const size_t nb = 4 * ((size_t)D + 1);
+    BufPtr cursor = s->alloc(nb);
+    {
+      KernelTimer kt(s, "vu_index", 24.0 * m);
+      ix.uiadj = s->alloc(8 * m);
+      HIP_CHECK(hipMemcpyAsync(cursor->p, ix.rowptr->p, nb, hipMemcpyDeviceToDevice, s->stream));
+      hipLaunchKernelGGL(k_vu_fill_in, dim3(grid_for(m, 256, 256 * 64)), dim3(256), 0, s->stream,
+                         (const uint32_t *)ix.orow->p, (const uint32_t *)ix.ocol->p, D, m, (uint32_t *)cursor->p,
+                         (uint2 *)ix.uiadj->p);
+      KERNEL_CHECK();
+      ix.usorder = vt_source_order(s, ix, (const uint32_t *)ix.rowptr->p);
+    }
+    s->sync();
+  }
+}
+
+// reach[j] of every source j by enumeration: trails (directed, 2 ≤ lower ≤
+// upper ≤ 4) or the undirected steps (0 ≤ lower ≤ upper ≤ 4)
+static void vt_enumerate(Session *s, VrIndex &ix, bool undirected, int lower, int upper, bool expand,
+                         int64_t *reach) {
+  vt_build(s, ix, undirected);
+  // the kernels by upper bound
+  static const decltype(&k_vt_trails<2>) trails[5] = {nullptr, nullptr, k_vt_trails<2>, k_vt_trails<3>,
+                                                      k_vt_trails<4>};
+  static const decltype(&k_vu_steps<0>) steps[5] = {k_vu_steps<0>, k_vu_steps<1>, k_vu_steps<2>, k_vu_steps<3>,
+                                                    k_vu_steps<4>};
   static std::once_flag attr_once;
   std::call_once(attr_once, [] {
-    for (Kern k : kerns)
-      HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)VT_LDS_MAX));
+    for (int u = 0; u <= 4; ++u)
+      for (const void *k : {(const void *)trails[u], (const void *)steps[u]})
+        if (k) HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)VT_LDS_MAX));
   });
   const uint32_t D = ix.D;
-  const size_t lds = 4 * ((size_t)(((D + 31) / 32 + 3) & ~3u) + 4);
-  KernelTimer kt(s, "vu_steps", 12.0 * m);
-  hipLaunchKernelGGL(kerns[upper], dim3((unsigned)ix.ns), dim3(VT_BLOCK), lds, s->stream,
-                     (const uint32_t *)ix.orow->p, (const uint32_t *)ix.uocol->p, (const uint32_t *)ix.rowptr->p,
-                     (const uint2 *)ix.uiadj->p, (const uint64_t *)ix.usorder->p, (const int64_t *)ix.src_nodes->p,
-                     (const uint32_t *)ix.tmask->p, D, lower, reach);
+  // LDS: the bitmap, the trails' expanded-rows bitmap while two fit (D up to
+  // about 655 k), the two control words (padded to 16 B)
+  const size_t wp = (size_t)(((D + 31) / 32 + 3) & ~3u);
+  const int use_ex = !undirected && expand && 4 * (2 * wp + 4) <= VT_LDS_MAX;
+  const size_t lds = 4 * ((use_ex ? 2 * wp : wp) + 4);
+  const uint32_t *orow = (const uint32_t *)ix.orow->p, *ocol = (const uint32_t *)ix.ocol->p;
+  const int64_t *src_nodes = (const int64_t *)ix.src_nodes->p;
+  const uint32_t *tmask = (const uint32_t *)ix.tmask->p;
+  KernelTimer kt(s, undirected ? "vu_steps" : "vt_trails", (undirected ? 12.0 : 4.0) * ix.m);
+  if (undirected)
+    hipLaunchKernelGGL(steps[upper], dim3((unsigned)ix.ns), dim3(VT_BLOCK), lds, s->stream, orow, ocol,
+                       (const uint32_t *)ix.rowptr->p, (const uint2 *)ix.uiadj->p, (const uint64_t *)ix.usorder->p,
+                       src_nodes, tmask, D, lower, reach);
+  else
+    hipLaunchKernelGGL(trails[upper], dim3((unsigned)ix.ns), dim3(VT_BLOCK), lds, s->stream, orow, ocol,
+                       (const uint64_t *)ix.sorder->p, src_nodes, tmask, D, lower, use_ex, reach);
   KERNEL_CHECK();
 }
 
@@ -866,41 +875,33 @@ static std::shared_ptr<VrIndex> vr_build(Session *s, const ColPtr &rsrc, const C
   // duplicates would be merged by the DISTINCT anyway)
   int64_t ns = 0;
   BufPtr src_nodes = compact_flags(s, (const uint8_t *)sflag->p, D, &ns);
-  // 3. in-CSR by target
-  BufPtr deg = s->alloc(4 * ((int64_t)D + 1)), rowptr = s->alloc(4 * ((int64_t)D + 1));
-  BufPtr cursor = s->alloc(4 * ((int64_t)D + 1)), cols = s->alloc(4 * m);
-  HIP_CHECK(hipMemsetAsync(deg->p, 0, 4 * ((int64_t)D + 1), s->stream));
+  // 3. in-CSR by target: rows keyed by the rel's target, holding its source
   {
     KernelTimer kt(s, "vr_csr", 16.0 * m);
-    hipLaunchKernelGGL(k_vr_indeg, dim3(g), dim3(256), 0, s->stream, (const uint32_t *)di->p, m,
-                       (uint32_t *)deg->p);
-    BufPtr tot = s->alloc(16);
-    exclusive_scan_u32_async(s, (const uint32_t *)deg->p, (uint32_t *)rowptr->p, (int64_t)D + 1,
-                             (uint32_t *)tot->p);
-    HIP_CHECK(hipMemcpyAsync(cursor->p, rowptr->p, 4 * ((int64_t)D + 1), hipMemcpyDeviceToDevice,
-                             s->stream));
-    hipLaunchKernelGGL(k_vr_fill, dim3(g), dim3(256), 0, s->stream, (const uint32_t *)si->p,
-                       (const uint32_t *)di->p, m, (uint32_t *)cursor->p, (uint32_t *)cols->p);
-    KERNEL_CHECK();
+    vr_csr(s, (const uint32_t *)di->p, (const uint32_t *)si->p, m, D, ix->rowptr, ix->cols);
   }
-  cursor.reset();
-  BufPtr order;
   {
     BufPtr dkey = s->alloc(8 * (int64_t)D);
-    order = s->alloc(8 * (int64_t)D);
+    ix->order = s->alloc(8 * (int64_t)D);
     hipLaunchKernelGGL(k_vr_degkey, dim3(grid_for(D, 256)), dim3(256), 0, s->stream,
-                       (const uint32_t *)rowptr->p, D, (uint64_t *)dkey->p);
+                       (const uint32_t *)ix->rowptr->p, D, (uint64_t *)dkey->p);
     KERNEL_CHECK();
     vr_rocprim(s, [&](void *t, size_t &n) {
-      return rocprim::radix_sort_keys(t, n, (const uint64_t *)dkey->p, (uint64_t *)order->p,
+      return rocprim::radix_sort_keys(t, n, (const uint64_t *)dkey->p, (uint64_t *)ix->order->p,
                                       (size_t)D, 0, 64, s->stream);
     });
   }
-  BufPtr srcpos = s->alloc(4 * (int64_t)D);
-  HIP_CHECK(hipMemsetAsync(srcpos->p, 0xFF, 4 * (size_t)D, s->stream));
+  ix->srcpos = s->alloc(4 * (int64_t)D);
+  HIP_CHECK(hipMemsetAsync(ix->srcpos->p, 0xFF, 4 * (size_t)D, s->stream));
   hipLaunchKernelGGL(k_vr_srcpos, dim3(grid_for(ns, 256)), dim3(256), 0, s->stream,
-                     (const int64_t *)src_nodes->p, ns, (int32_t *)srcpos->p);
+                     (const int64_t *)src_nodes->p, ns, (int32_t *)ix->srcpos->p);
   KERNEL_CHECK();
+  ix->rdst = rdst;
+  ix->sid = sid;
+  ix->tid = tid;
+  ix->m = m;
+  ix->ns_in = ns_in;
+  ix->nt = nt;
   ix->D = D;
   ix->ns = ns;
   ix->dict = dict;
@@ -908,49 +909,31 @@ static std::shared_ptr<VrIndex> vr_build(Session *s, const ColPtr &rsrc, const C
   ix->di = di;
   ix->tflag = tflag;
   ix->src_nodes = src_nodes;
-  ix->rowptr = rowptr;
-  ix->cols = cols;
-  ix->order = order;
-  ix->srcpos = srcpos;
   return ix;
 }
 
-struct VrCache {
-  std::weak_ptr<Column> rdst, sid, tid;
-  int64_t m = 0, ns_in = 0, nt = 0;
-  std::shared_ptr<VrIndex> ix;
-};
-
 // 4. MS-BFS in batches of 64·K sources: reach[j] of every source j
-static void vr_bfs(Session *s, const VrIndex &ixr, int64_t m, int upper, bool include_self,
+static void vr_bfs(Session *s, const VrIndex &ix, const VrKnobs &kn, int upper, bool include_self,
                    const BufPtr &reach) {
-  const VrIndex *ix = &ixr;
-  const uint32_t D = ix->D;
-  const int64_t ns = ix->ns;
-  const BufPtr &si = ix->si, &di = ix->di, &tflag = ix->tflag, &src_nodes = ix->src_nodes;
-  const BufPtr &rowptr = ix->rowptr, &cols = ix->cols, &order = ix->order, &srcpos = ix->srcpos;
+  const uint32_t D = ix.D;
+  const int64_t m = ix.m, ns = ix.ns;
   const unsigned g = grid_for(m, 256, 256 * 64);
-  // CAPF_VR_BUDGET (tests): a smaller state budget in bytes → more source batches
-  const char *vb = getenv("CAPF_VR_BUDGET");
-  const double budget = vb && atof(vb) > 0 ? atof(vb) : (double)VR_STATE_BUDGET;
-  const int64_t kmax = std::max<int64_t>(1, (int64_t)(budget / (24.0 * D)));
+  const int64_t kmax = std::max<int64_t>(1, (int64_t)(kn.budget / (24.0 * D)));
   const int64_t K = std::min<int64_t>((ns + 63) / 64, kmax);
   BufPtr fa = s->alloc(8 * (int64_t)D * K), fb = s->alloc(8 * (int64_t)D * K);
   BufPtr vis = s->alloc(8 * (int64_t)D * K);
   const unsigned glev = grid_for((int64_t)D * K, 256, (int64_t)s->num_cus * 32);
-  const char *vce = getenv("CAPF_VR_COUNT");  // 0 (tuning): the ballot-transpose count
   // the bit-sliced count takes row chunks on gridDim.y (≤ 65535): beyond that
   // (D > 2^26 nodes) the ballot-transpose count, whose grid is 1-D over sources
-  const bool bs_count = !(vce && atoi(vce) == 0) &&
-                        (int64_t)D <= (int64_t)65535 * (1024 / WAVE) * VR_CR;
+  const bool bs_count = kn.count_bs && (int64_t)D <= (int64_t)65535 * (1024 / WAVE) * VR_CR;
   for (int64_t s0 = 0; s0 < ns; s0 += 64 * K) {
     const int64_t nb = std::min<int64_t>(64 * K, ns - s0);
     HIP_CHECK(hipMemsetAsync(fb->p, 0, 8 * (size_t)D * K, s->stream));
     HIP_CHECK(hipMemsetAsync(vis->p, 0, 8 * (size_t)D * K, s->stream));
     {
       KernelTimer kt(s, "vr_push1", 12.0 * m);
-      hipLaunchKernelGGL(k_vr_push1, dim3(g), dim3(256), 0, s->stream, (const uint32_t *)si->p,
-                         (const uint32_t *)di->p, m, (const int32_t *)srcpos->p, s0, nb, K,
+      hipLaunchKernelGGL(k_vr_push1, dim3(g), dim3(256), 0, s->stream, (const uint32_t *)ix.si->p,
+                         (const uint32_t *)ix.di->p, m, (const int32_t *)ix.srcpos->p, s0, nb, K,
                          (unsigned long long *)vis->p, (unsigned long long *)fb->p);
       KERNEL_CHECK();
     }
@@ -958,8 +941,8 @@ static void vr_bfs(Session *s, const VrIndex &ixr, int64_t m, int upper, bool in
     for (int l = 2; l <= upper; ++l) {
       KernelTimer kt(s, "vr_level", 8.0 * K * ((double)m + 3.0 * D));
       hipLaunchKernelGGL(k_vr_level, dim3(glev), dim3(256), 0, s->stream,
-                         (const uint32_t *)rowptr->p, (const uint32_t *)cols->p,
-                         (const uint64_t *)order->p, cur, nxt,
+                         (const uint32_t *)ix.rowptr->p, (const uint32_t *)ix.cols->p,
+                         (const uint64_t *)ix.order->p, cur, nxt,
                          (unsigned long long *)vis->p, (int64_t)D, K, l == upper ? 1 : 0);
       KERNEL_CHECK();
       std::swap(cur, nxt);
@@ -971,26 +954,35 @@ static void vr_bfs(Session *s, const VrIndex &ixr, int64_t m, int upper, bool in
         const int64_t kw = (nb + 63) / 64;  // source words of this batch
         const int64_t cg = (D + (int64_t)(1024 / WAVE) * VR_CR - 1) / ((int64_t)(1024 / WAVE) * VR_CR);
         hipLaunchKernelGGL(k_vr_count_bs, dim3((unsigned)((kw + 63) / 64), (unsigned)cg), dim3(1024), 0,
-                           s->stream, (const unsigned long long *)vis->p, (const uint8_t *)tflag->p,
+                           s->stream, (const unsigned long long *)vis->p, (const uint8_t *)ix.tflag->p,
                            (int64_t)D, K, s0, nb, (unsigned long long *)reach->p);
       } else {
         hipLaunchKernelGGL(k_vr_count, dim3((unsigned)((nb + 63) / 64)), dim3(256), 0, s->stream,
-                           (const unsigned long long *)vis->p, (const uint8_t *)tflag->p, (int64_t)D,
+                           (const unsigned long long *)vis->p, (const uint8_t *)ix.tflag->p, (int64_t)D,
                            K, s0, nb, (int64_t *)reach->p);
       }
       KERNEL_CHECK();
       if (include_self) {
         hipLaunchKernelGGL(k_vr_self, dim3(grid_for(nb, 256)), dim3(256), 0, s->stream,
-                           (const unsigned long long *)vis->p, (const uint8_t *)tflag->p,
-                           (const int64_t *)src_nodes->p, K, s0, nb, (int64_t *)reach->p);
+                           (const unsigned long long *)vis->p, (const uint8_t *)ix.tflag->p,
+                           (const int64_t *)ix.src_nodes->p, K, s0, nb, (int64_t *)reach->p);
         KERNEL_CHECK();
       }
     }
   }
 }
 
-static DataPtr vr_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m, const ColPtr &sid,
-                       int64_t ns_in, const ColPtr &tid, int64_t nt, int lower, int upper, bool undirected) {
+ReachMethod reach_method(bool undirected, int lower, int upper) {
+  if (undirected) return 0 <= lower && lower <= upper && upper <= 4 ? ReachMethod::STEPS : ReachMethod::NONE;
+  if (lower >= 2) return lower <= upper && upper <= 4 ? ReachMethod::TRAILS : ReachMethod::NONE;
+  return lower >= 0 && 1 <= upper && upper <= 64 ? ReachMethod::BFS : ReachMethod::NONE;
+}
+
+DataPtr var_length_reach_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m, const ColPtr &sid,
+                              int64_t ns_in, const ColPtr &tid, int64_t nt, int lower, int upper,
+                              bool undirected) {
+  const ReachMethod rm = reach_method(undirected, lower, upper);
+  if (rm == ReachMethod::NONE) return nullptr;
   const bool include_self = lower == 0;
   auto out = std::make_shared<Data>();
   out->cols = {make_column(s, Type::Int64, 0, false), make_column(s, Type::Int64, 0, false)};
@@ -1008,38 +1000,22 @@ static DataPtr vr_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64
   std::shared_ptr<VrIndex> ix;
   {
     std::lock_guard<std::mutex> lk(rsrc->mu);
-    if (rsrc->vr_index) {
-      auto vc = std::static_pointer_cast<VrCache>(rsrc->vr_index);
-      if (vc->rdst.lock() == rdst && vc->sid.lock() == sid && vc->tid.lock() == tid && vc->m == m &&
-          vc->ns_in == ns_in && vc->nt == nt)
-        ix = vc->ix;
-    }
+    ix = rsrc->vr_index;
   }
-  if (!ix) {
+  if (!ix || ix->rdst.lock() != rdst || ix->sid.lock() != sid || ix->tid.lock() != tid || ix->m != m ||
+      ix->ns_in != ns_in || ix->nt != nt) {
     ix = vr_build(s, rsrc, rdst, m, sid, ns_in, tid, nt);
-    auto vc = std::make_shared<VrCache>();
-    vc->rdst = rdst;
-    vc->sid = sid;
-    vc->tid = tid;
-    vc->m = m;
-    vc->ns_in = ns_in;
-    vc->nt = nt;
-    vc->ix = ix;
     std::lock_guard<std::mutex> lk(rsrc->mu);
-    rsrc->vr_index = vc;
+    rsrc->vr_index = ix;
   }
   const uint32_t D = ix->D;
   const int64_t ns = ix->ns;
-  // CAPF_VT_MAX_NODES (tests): a lower node limit of the trail kernel
-  const char *vm = getenv("CAPF_VT_MAX_NODES");
-  const int64_t vt_max = vm && atoll(vm) > 0 ? std::min<int64_t>(atoll(vm), VT_MAX_NODES) : VT_MAX_NODES;
-  if ((undirected || lower >= 2) && ((int64_t)D > vt_max || m >= (int64_t(1) << 31))) return nullptr;
-  const uint64_t *dk = (const uint64_t *)ix->dict->p;
-  const BufPtr &src_nodes = ix->src_nodes;
+  const VrKnobs kn = vr_knobs();
+  // the enumeration kernels hold a D-bit bitmap in LDS and rel positions below 2^31
+  if (rm != ReachMethod::BFS && ((int64_t)D > kn.max_nodes || m >= (int64_t(1) << 31))) return nullptr;
   BufPtr reach = s->alloc(8 * std::max<int64_t>(ns, 1));
-  if (undirected) vu_reach(s, *ix, m, lower, upper, (int64_t *)reach->p);
-  else if (lower >= 2) vt_reach(s, *ix, m, lower, upper, (int64_t *)reach->p);
-  else vr_bfs(s, *ix, m, upper, include_self, reach);
+  if (rm == ReachMethod::BFS) vr_bfs(s, *ix, kn, upper, include_self, reach);
+  else vt_enumerate(s, *ix, rm == ReachMethod::STEPS, lower, upper, kn.expand, (int64_t *)reach->p);
   // 5. rows (a, reach) for the sources that reach at least one target (every
   // source from lower bound 0)
   BufPtr pos = s->alloc(std::max<int64_t>(ns, 1));
@@ -1051,7 +1027,7 @@ static DataPtr vr_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64
   ColPtr a = make_column(s, Type::Int64, nr, false), r = make_column(s, Type::Int64, nr, false);
   if (nr > 0) {
     hipLaunchKernelGGL(k_vr_out, dim3(grid_for(nr, 256)), dim3(256), 0, s->stream,
-                       (const int64_t *)rows->p, nr, (const int64_t *)src_nodes->p, dk,
+                       (const int64_t *)rows->p, nr, (const int64_t *)ix->src_nodes->p, (const uint64_t *)ix->dict->p,
                        (const int64_t *)reach->p, (int64_t *)a->data->p, (int64_t *)r->data->p);
     KERNEL_CHECK();
   }
@@ -1059,19 +1035,6 @@ static DataPtr vr_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64
   out->nrows = nr;
   out->cols = {a, r};
   return out;
-}
-
-DataPtr var_length_reach_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m,
-                                const ColPtr &sid, int64_t ns_in, const ColPtr &tid, int64_t nt,
-                                int lower, int upper) {
-  return vr_rows(s, rsrc, rdst, m, sid, ns_in, tid, nt, lower, upper, false);
-}
-
-DataPtr var_length_reach_undirected_rows(Session *s, const ColPtr &rsrc, const ColPtr &rdst, int64_t m,
-                                           const ColPtr &sid, int64_t ns_in, const ColPtr &tid, int64_t nt,
-                                           int lower, int upper) {
-  if (lower < 0 || lower > upper || upper > 4) return nullptr;
-  return vr_rows(s, rsrc, rdst, m, sid, ns_in, tid, nt, lower, upper, true);
 }
 
 static ColPtr int_column_of(const NodePtr &nd, const DataPtr &d, const char *name) {
@@ -1094,14 +1057,11 @@ static capf_status vr_entry(capf_session *cs, capf_table *rels, const char *src_
     if (!cs || !rels || !src_col || !dst_col || !sources || !source_id_col || !targets ||
         !target_id_col || !out_source_col || !out_reach_col || !out)
       illegal("null argument");
-    if (undirected) {
-      if (!(0 <= lower && lower <= upper && upper <= 4))
-        not_impl("undirected var-length reach is fused for 0 <= lower <= upper <= 4 only");
-    } else {
+    if (reach_method(undirected, lower, upper) == ReachMethod::NONE) {  // say which side of the domain
+      if (undirected) not_impl("undirected var-length reach is fused for 0 <= lower <= upper <= 4 only");
       if (lower < 0) not_impl("var-length reach: negative lower bound");
-      if (lower >= 2 && !(lower <= upper && upper <= 4))
-        not_impl("var-length reach: lower bounds from 2 are fused for 2 <= lower <= upper <= 4 only");
-      if (upper < 1 || upper > 64) illegal("var-length reach: upper bound out of range");
+      if (lower >= 2) not_impl("var-length reach: lower bounds from 2 are fused for 2 <= lower <= upper <= 4 only");
+      illegal("var-length reach: upper bound out of range");
     }
     if (!strcmp(out_source_col, out_reach_col)) illegal("output column names must differ");
     Session *s = &cs->impl;
@@ -1110,9 +1070,7 @@ static capf_status vr_entry(capf_session *cs, capf_table *rels, const char *src_
     ColPtr rs = int_column_of(rels->node, dr, src_col), rd = int_column_of(rels->node, dr, dst_col);
     ColPtr si = int_column_of(sources->node, ds, source_id_col);
     ColPtr ti = int_column_of(targets->node, dt, target_id_col);
-    DataPtr d = undirected ? var_length_reach_undirected_rows(s, rs, rd, dr->nrows, si, ds->nrows, ti, dt->nrows,
-                                                              lower, upper)
-                           : var_length_reach_rows(s, rs, rd, dr->nrows, si, ds->nrows, ti, dt->nrows, lower, upper);
+    DataPtr d = var_length_reach_rows(s, rs, rd, dr->nrows, si, ds->nrows, ti, dt->nrows, lower, upper, undirected);
     if (!d)
       not_impl(undirected ? "undirected var-length reach: more nodes than the step kernel's LDS bitmap holds (2^20)"
                           : "var-length reach: more nodes than the trail kernel's LDS bitmap holds (2^20)");

@@ -2,7 +2,7 @@
 (VarLengthExpand join chain + isomorphism filters + UNION ALL, DISTINCT,
 GROUP BY — VarLengthExpandPlanner.scala:82-259) through the Table SPI; the
 runtime recognises Group(a; count(*)) ∘ Distinct(a, b) ∘ UNION ALL of the
-chains in its plan DAG (fused_count.hip::try_fused_reach) and runs the BFS of
+chains in its plan DAG (reach_plan.hip::try_fused_reach) and runs the BFS of
 csrc/var_length_reach.hip.  Checked against (1) the scipy matrix-power
 restatement (oracle/reach.py), (2) the unfused relational plan on the GPU
 (CAPF_FUSED_REACH=0) and (3) the isomorphic-path brute force on the

@@ -4,7 +4,7 @@ From lower bound 2 on the DISTINCT (a, b) pairs of the relational lowering
 (join chain with all NOT(e_i = e_j) filters, UNION ALL, DISTINCT, GROUP BY)
 are the pairs joined by a TRAIL — a path whose relationships are pairwise
 distinct — not by a walk.  The runtime recognises the shape
-(fused_count.hip::try_fused_reach) and enumerates the trails per source
+(reach_plan.hip::try_fused_reach) and enumerates the trails per source
 (var_length_reach.hip::k_vt_trails).  Expected values: a plain-Python trail
 enumerator, itself checked against the relational lowering on the CPU oracle.
 The graphs are sparse, with self-loops and parallel rels: on the dense R-MAT

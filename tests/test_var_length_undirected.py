@@ -11,7 +11,7 @@ and a state of depth max(l, 1)..u pairs a with its node.  That is neither the
 trails of the symmetrised graph nor any walk, so the expected values come
 from `steps_reach`, a plain-Python enumerator of the automaton that the CPU
 tests tie to the relational lowering on the oracle.  The runtime recognises
-the shape (fused_count.hip::try_fused_reach, unions hoisted over the joins)
+the shape (reach_plan.hip::try_fused_reach, unions hoisted over the joins)
 and enumerates the steps per source (var_length_reach.hip::k_vu_steps)."""
 import functools
 
