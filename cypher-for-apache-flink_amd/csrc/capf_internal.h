@@ -428,6 +428,16 @@ struct Session {
   };
   std::mutex match_mu;
   std::vector<StrMatchTable> match_tables;
+  // device hash index of the dictionary (string_fn.hip): an open-addressed
+  // table of codes (−1 empty, `slots` a power of two, at most half full) keyed
+  // by the 64-bit hash of each string's bytes, and those hashes by code;
+  // extended over the codes interned since, rebuilt when it passes half full
+  struct StrIndex {
+    BufPtr tab, hashes;
+    size_t n = 0, slots = 0, hash_cap = 0;  // codes covered, table slots, hashes allocated
+  };
+  std::mutex index_mu;
+  StrIndex str_index;
   // small device scratch for scalar results
   int64_t *d_scalars = nullptr;  // 64 slots
   int64_t *h_scalars = nullptr;  // pinned mirror
@@ -618,6 +628,24 @@ BufPtr string_match_table(Session *s, int kind, int64_t pattern_code, size_t *n)
 // (the strings it does not cover yet are at most the rows), false = row by
 // row.  CAPF_STR_MATCH=rows|dict forces one.
 bool string_match_by_table(Session *s, int kind, int64_t pattern_code, int64_t nrows);
+// Bytes from which a string goes to a wave instead of a thread (CAPF_STR_LONG, default 256).
+int64_t string_long_threshold();
+// The strings a device step made against a snapshot of n0 dictionary strings
+// (heap end `base`), as codes n0, n0 + 1, …: n_new end offsets (absolute, from
+// `base` on) and nb bytes, on the device and copied to the host.  While the
+// dictionary still holds n0 strings they are appended to the heap device to
+// device and to the host dictionary; when another thread interned meanwhile,
+// each is resolved through the host map instead (the heap catches up at its
+// next use).  codes[r] = the code of new string r.
+void string_heap_append(Session *s, size_t n0, int64_t base, const int64_t *d_offs, const uint8_t *d_bytes,
+                        const int64_t *h_offs, const char *h_bytes, int64_t n_new, int64_t nb,
+                        std::vector<int64_t> &codes);
+// A string function (CAPF_STR_FN_*) of n dictionary strings — the codes src[i]
+// (−1 NULL), or c0 + i when src is null — evaluated on the heap and interned
+// on the device (string_fn.hip): out[i] (host) = the result's code, −1 NULL,
+// −2 "evaluate on the host".
+void string_fn_codes(Session *s, int32_t fn, int64_t iarg0, int64_t iarg1, int64_t lit0, int64_t lit1,
+                     const int64_t *src, int64_t c0, int64_t n, int64_t *out);
 // Record an error for capf_last_error() (used by entry points outside runtime.cpp).
 int32_t record_error(int32_t code, const char *msg);
 

@@ -907,6 +907,60 @@ const int64_t *string_order_table(Session *s, size_t *n) {
 // word ahead.
 constexpr int64_t HEAP_PAD = 16;
 
+// Room for m strings of `end` bytes in all (str_mu held): geometric
+// capacities; a grown buffer takes its content device to device.
+static void heap_reserve(Session *s, size_t m, int64_t end) {
+  const size_t have = s->d_heap_off ? s->d_heap_n : 0;
+  if (m + 1 > s->d_heap_off_cap) {
+    const size_t cap = std::max<size_t>(2 * s->d_heap_off_cap, std::max<size_t>(m + 1, 1024));
+    BufPtr nb = s->alloc(8 * cap);
+    if (s->d_heap_off)
+      HIP_CHECK(hipMemcpyAsync(nb->p, s->d_heap_off->p, 8 * (have + 1), hipMemcpyDeviceToDevice, s->stream));
+    s->d_heap_off = nb;
+    s->d_heap_off_cap = cap;
+  }
+  if (end + HEAP_PAD > s->d_heap_bytes_cap || !s->d_heap_bytes) {
+    const int64_t cap = std::max<int64_t>(2 * s->d_heap_bytes_cap, std::max<int64_t>(end + HEAP_PAD, 1 << 16));
+    BufPtr nb = s->alloc((size_t)cap);
+    if (s->d_heap_bytes && s->d_heap_nbytes > 0)
+      HIP_CHECK(hipMemcpyAsync(nb->p, s->d_heap_bytes->p, (size_t)s->d_heap_nbytes, hipMemcpyDeviceToDevice,
+                               s->stream));
+    s->d_heap_bytes = nb;
+    s->d_heap_bytes_cap = cap;
+  }
+}
+
+void string_heap_append(Session *s, size_t n0, int64_t base, const int64_t *d_offs, const uint8_t *d_bytes,
+                        const int64_t *h_offs, const char *h_bytes, int64_t n_new, int64_t nb,
+                        std::vector<int64_t> &codes) {
+  codes.resize((size_t)n_new);
+  std::lock_guard<std::mutex> lk(s->str_mu);
+  const bool same = s->strings.size() == n0 && s->d_heap_off && s->d_heap_n == n0 && s->d_heap_nbytes == base;
+  if (same) {  // codes n0.. in order; the heap grows device to device
+    heap_reserve(s, n0 + (size_t)n_new, base + nb);
+    HIP_CHECK(hipMemcpyAsync((int64_t *)s->d_heap_off->p + n0 + 1, d_offs, 8 * (size_t)n_new,
+                             hipMemcpyDeviceToDevice, s->stream));
+    if (nb > 0)
+      HIP_CHECK(hipMemcpyAsync((uint8_t *)s->d_heap_bytes->p + base, d_bytes, (size_t)nb, hipMemcpyDeviceToDevice,
+                               s->stream));
+    s->d_heap_n = n0 + (size_t)n_new;
+    s->d_heap_nbytes = base + nb;
+  }
+  int64_t b = base;
+  for (int64_t r = 0; r < n_new; ++r) {
+    std::string str(h_bytes + (b - base), (size_t)(h_offs[r] - b));
+    b = h_offs[r];
+    auto it = same ? s->string_codes.end() : s->string_codes.find(str);
+    if (it != s->string_codes.end()) {
+      codes[(size_t)r] = it->second;
+      continue;
+    }
+    codes[(size_t)r] = (int64_t)s->strings.size();
+    s->string_codes.emplace(str, codes[(size_t)r]);
+    s->strings.push_back(std::move(str));
+  }
+}
+
 StringHeap string_heap(Session *s, size_t *n) {
   std::lock_guard<std::mutex> lk(s->str_mu);
   const size_t m = s->strings.size(), have = s->d_heap_off ? s->d_heap_n : 0;
@@ -921,24 +975,7 @@ StringHeap string_heap(Session *s, size_t *n) {
       end += (int64_t)s->strings[i].size();
       off.push_back(end);
     }
-    // geometric capacities; a grown buffer takes its content device to device
-    if (m + 1 > s->d_heap_off_cap) {
-      const size_t cap = std::max<size_t>(2 * s->d_heap_off_cap, std::max<size_t>(m + 1, 1024));
-      BufPtr nb = s->alloc(8 * cap);
-      if (s->d_heap_off)
-        HIP_CHECK(hipMemcpyAsync(nb->p, s->d_heap_off->p, 8 * (have + 1), hipMemcpyDeviceToDevice, s->stream));
-      s->d_heap_off = nb;
-      s->d_heap_off_cap = cap;
-    }
-    if (end + HEAP_PAD > s->d_heap_bytes_cap || !s->d_heap_bytes) {
-      const int64_t cap = std::max<int64_t>(2 * s->d_heap_bytes_cap, std::max<int64_t>(end + HEAP_PAD, 1 << 16));
-      BufPtr nb = s->alloc((size_t)cap);
-      if (s->d_heap_bytes && s->d_heap_nbytes > 0)
-        HIP_CHECK(hipMemcpyAsync(nb->p, s->d_heap_bytes->p, (size_t)s->d_heap_nbytes, hipMemcpyDeviceToDevice,
-                                 s->stream));
-      s->d_heap_bytes = nb;
-      s->d_heap_bytes_cap = cap;
-    }
+    heap_reserve(s, m, end);
     const size_t first = m + 1 - off.size();  // index of the first offset uploaded
     HIP_CHECK(hipMemcpyAsync((int64_t *)s->d_heap_off->p + first, off.data(), 8 * off.size(), hipMemcpyHostToDevice,
                              s->stream));
@@ -1333,6 +1370,16 @@ capf_status capf_string_digest(capf_session *cs, int64_t *count, uint64_t *diges
   }
   *count = (int64_t)s.strings.size();
   *digest = h;
+  CAPF_API_END
+}
+
+capf_status capf_string_fn_codes(capf_session *cs, int32_t fn, int64_t iarg0, int64_t iarg1, int64_t lit0,
+                                 int64_t lit1, const int64_t *src, int64_t c0, int64_t n, int64_t *out) {
+  CAPF_API_BEGIN
+  need(cs, "session");
+  if (n < 0) illegal("negative count");
+  if (n > 0) need(out, "out");
+  string_fn_codes(&cs->impl, fn, iarg0, iarg1, lit0, lit1, src, c0, n, out);
   CAPF_API_END
 }
 

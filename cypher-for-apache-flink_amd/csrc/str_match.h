@@ -29,6 +29,19 @@ struct PatRef {
   int64_t off, len;
 };
 
+constexpr int PAT_LDS_BYTES = 256;  // the pattern staging area
+
+// The block's pattern (dictionary code pcode): staged into s_pat (PAT_LDS_BYTES
+// / 4 words) when it fits.  Every thread of the block calls this.
+__device__ inline PatRef stage_pattern(const int64_t *off, const uint8_t *bytes, int64_t pcode, uint32_t *s_pat) {
+  const int64_t poff = off[pcode], plen = off[pcode + 1] - poff;
+  const bool staged = plen <= PAT_LDS_BYTES;
+  if (staged)
+    for (int i = threadIdx.x; 4 * (int64_t)i < plen; i += blockDim.x) s_pat[i] = heap_u32(bytes, poff + 4 * (int64_t)i);
+  __syncthreads();
+  return PatRef{staged ? s_pat : nullptr, poff, plen};
+}
+
 // Pattern bytes [i, i + 4), i a multiple of 4.
 __device__ inline uint32_t pat_u32(const uint8_t *bytes, const PatRef &p, int64_t i) {
   return p.lds ? p.lds[i >> 2] : heap_u32(bytes, p.off + i);

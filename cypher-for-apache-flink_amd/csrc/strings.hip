@@ -30,20 +30,9 @@
 
 namespace capf {
 
-constexpr int PAT_LDS_BYTES = 256;  // the pattern staging area
 constexpr int SM_BLOCK = 256;
 constexpr int64_t STR_LONG_DEFAULT = 256;
 constexpr int LONG_ILP = 4;  // strides of 64 start positions a wave tests per ballot
-
-// The block's pattern: staged into s_pat (PAT_LDS_BYTES / 4 words) when it fits.
-__device__ inline PatRef stage_pattern(const int64_t *off, const uint8_t *bytes, int64_t pcode, uint32_t *s_pat) {
-  const int64_t poff = off[pcode], plen = off[pcode + 1] - poff;
-  const bool staged = plen <= PAT_LDS_BYTES;
-  if (staged)
-    for (int i = threadIdx.x; 4 * (int64_t)i < plen; i += blockDim.x) s_pat[i] = heap_u32(bytes, poff + 4 * (int64_t)i);
-  __syncthreads();
-  return PatRef{staged ? s_pat : nullptr, poff, plen};
-}
 
 __global__ __launch_bounds__(SM_BLOCK) void k_str_match(const int64_t *off, const uint8_t *bytes, int64_t c0,
                                                          int64_t c1, int kind, int64_t pcode, int64_t long_len,
@@ -93,8 +82,8 @@ __global__ __launch_bounds__(SM_BLOCK) void k_str_contains_long(const int64_t *o
   }
 }
 
-static int64_t long_threshold() {
-  const char *e = getenv("CAPF_STR_LONG");  // bytes from which CONTAINS gives a subject to a wave
+int64_t string_long_threshold() {
+  const char *e = getenv("CAPF_STR_LONG");  // bytes from which a string is given to a wave
   const long long v = e ? atoll(e) : 0;
   return v > 0 ? (int64_t)v : STR_LONG_DEFAULT;
 }
@@ -120,7 +109,7 @@ static void fill_match_table(Session *s, const StringHeap &h, int kind, int64_t 
   {
     KernelTimer kt(s, "str_match", heap_bytes);
     hipLaunchKernelGGL(k_str_match, dim3(grid_for(m, SM_BLOCK)), dim3(SM_BLOCK), 0, s->stream, off, bytes, c0, c1,
-                       kind, pcode, long_threshold(), table, work ? (int64_t *)work->p : nullptr,
+                       kind, pcode, string_long_threshold(), table, work ? (int64_t *)work->p : nullptr,
                        cnt ? (unsigned long long *)cnt->p : nullptr);
     KERNEL_CHECK();
   }

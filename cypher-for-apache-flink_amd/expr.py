@@ -486,6 +486,39 @@ def string_fn(key, sv):
 
 _STR_FUNCS = {"ToUpper": "upper", "ToLower": "lower", "Trim": "trim", "LTrim": "ltrim", "RTrim": "rtrim"}
 
+# CAPF_STR_FN_* (include/capf_gpu.h): the functions capf_string_fn_codes evaluates on the device heap
+STR_FN_IDS = {"upper": 0, "lower": 1, "trim": 2, "ltrim": 3, "rtrim": 4, "substring": 5, "concat_l": 6,
+              "concat_r": 7, "replace": 8}
+_REGEX_META = frozenset("\\^$.|?*+()[]{}")  # java.util.regex.Pattern's metacharacters
+
+
+def plain_replace_literal(search):
+    """replace's search literal is a Java regex (regexpReplace): True when it is
+    non-empty and holds no metacharacter, so that it matches exactly its own
+    text and the device may replace byte for byte."""
+    return bool(search) and not any(ch in _REGEX_META for ch in search)
+
+
+def device_string_fn(key, intern):
+    """capf_string_fn_codes' (fn, iarg0, iarg1, lit0, lit1) for the string
+    function `key` (string_fn's), literals interned by `intern`; None when the
+    host must evaluate it for every string (=~, a regex search literal, a
+    negative substring length)."""
+    fn = STR_FN_IDS.get(key[0])
+    if fn is None:
+        return None
+    if key[0] == "substring":
+        if key[2] < 0 or not all(-(1 << 63) <= v < (1 << 63) for v in key[1:3]):
+            return None
+        return fn, key[1], key[2], -1, -1
+    if key[0] in ("concat_l", "concat_r"):
+        return fn, 0, 0, intern(key[1]), -1
+    if key[0] == "replace":
+        if not plain_replace_literal(key[1]):
+            return None
+        return fn, 0, 0, intern(key[1]), intern(key[2])
+    return fn, 0, 0, -1, -1
+
 
 @dataclass(frozen=True)
 class ContainerIndex(Expr):

@@ -54,9 +54,11 @@ class GpuSession:
     def string_map(self, key):
         """Program name of the session code map of string function `key`
         (expr.string_fn) for CAPF_OP_STR_MAP: "\x01map:<id>".  The function runs
-        on the host over every dictionary string (results interned); a map is
-        extended and re-registered when the dictionary has grown since."""
-        from .expr import string_fn
+        over every dictionary string — on the device heap, results interned
+        there (string_fn_codes); on the host for the strings the device leaves
+        to it — and a map is extended and re-registered when the dictionary
+        has grown since."""
+        args = self._device_fn_args(key)  # (interns the literals: before the dictionary is measured)
         cnt, dig = c_int64(), c_uint64()
         _lib.call("capf_string_digest", self._h, byref(cnt), byref(dig))
         n = cnt.value
@@ -65,20 +67,48 @@ class GpuSession:
         ent = self._maps.get(key)
         if ent is not None and ent[0] >= n:
             return ent[2]
-        codes = list(ent[1]) if ent is not None else []
-        for c in range(len(codes), n):
-            r = string_fn(key, self.lookup(c))
-            codes.append(-1 if r is None else self.intern(r))
-        arr = (c_int64 * max(len(codes), 1))(*codes)
+        have = len(ent[1]) if ent is not None else 0
+        codes = np.empty(max(n, 1), dtype=np.int64)
+        if have:
+            codes[:have] = ent[1]
+        codes[have:n] = self.string_fn_codes(key, args, None, have, n - have)
+        arr = codes.ctypes.data_as(ctypes.POINTER(c_int64))
         mid = c_int32()
         if ent is None:
-            _lib.call("capf_session_code_map", self._h, arr, len(codes), byref(mid))
+            _lib.call("capf_session_code_map", self._h, arr, n, byref(mid))
         else:  # the same map grown (in place: no device table left behind per growth)
-            _lib.call("capf_session_code_map_extend", self._h, int(ent[2].rsplit(":", 1)[1]), arr, len(codes),
-                      byref(mid))
+            _lib.call("capf_session_code_map_extend", self._h, int(ent[2].rsplit(":", 1)[1]), arr, n, byref(mid))
         nm = "\x01map:%d" % mid.value
-        self._maps[key] = (n, codes, nm)
+        self._maps[key] = (n, codes[:n], nm)
         return nm
+
+    def _device_fn_args(self, key):
+        """capf_string_fn_codes' arguments for string function `key`, or None:
+        the host evaluates it (CAPF_STR_FN=host, or a function the device does
+        not know: expr.device_string_fn)."""
+        from .expr import device_string_fn
+        if os.environ.get("CAPF_STR_FN") == "host":
+            return None
+        return device_string_fn(key, self.intern)
+
+    def string_fn_codes(self, key, args, src, c0, n):
+        """The STRING codes (−1: NULL) string function `key` gives the n
+        dictionary strings `src` (an int64 array of codes, −1 NULL) or, src
+        None, c0 .. c0 + n: one capf_string_fn_codes call (args, from
+        _device_fn_args), then string_fn + intern for the strings it answers
+        −2 for — every string when args is None."""
+        from .expr import string_fn
+        out = np.full(n, -2, dtype=np.int64)
+        if src is not None:
+            src = np.ascontiguousarray(src, dtype=np.int64)
+            out[src < 0] = -1
+        if args is not None and n:
+            _lib.call("capf_string_fn_codes", self._h, *args, src.ctypes.data if src is not None else None,
+                      int(c0), int(n), out.ctypes.data)
+        for i in np.nonzero(out == -2)[0]:
+            r = string_fn(key, self.lookup(int(src[i]) if src is not None else c0 + int(i)))
+            out[i] = -1 if r is None else self.intern(r)
+        return out
 
     @classmethod
     def on_torch_stream(cls, device=0):
@@ -623,6 +653,10 @@ class GpuTable:
         t = self.withColumns(*zip(exprs, names), header=header, params=params).select(*names)
         types = [t.capf_type(c) for c in names]
         t = t.distinct(*names)
+        if isinstance(kind, tuple) and kind[0] == "fn":
+            args = self.session._device_fn_args(kind[1])
+            if args is not None:
+                return self._fn_value_map(kind[1], args, t, names[0])
         if t.size > VALUE_MAP_MAX:  # every distinct value becomes a host string and a dictionary entry
             raise _lib.NotImplementedException(
                 f"a new string per value over {t.size} distinct values (more than {VALUE_MAP_MAX})")
@@ -662,6 +696,28 @@ class GpuTable:
         cd = (c_int64 * max(n, 1))(*[e[1] for e in entries])
         mid = c_int32()
         _lib.call("capf_session_value_map", self.session._h, k1, k2, cd, n, byref(mid))
+        return "\x01vmap:%d" % mid.value
+
+    def _fn_value_map(self, key, args, t, col):
+        """The value map of string function `key` over the distinct STRING codes
+        in column `col` of t, mapped on the device heap (GpuSession.
+        string_fn_codes): no Python string per value, so no cap on their number."""
+        vals, valid = t.column_arrays(col)
+        codes = np.unique(vals[valid])
+        gather = getattr(self.session, "value_map_gather", None)
+        if gather is not None:
+            # distributed: every rank maps the sorted union of all ranks' codes (the
+            # dictionaries are equal), so each interns the same strings in the same order
+            codes = np.unique(np.concatenate([np.asarray(p, dtype=np.int64) for p in gather(codes)]))
+        out = self.session.string_fn_codes(key, args, codes, 0, len(codes))
+        keep = out >= 0  # (no entry: the lookup misses, NULL)
+        k1, cd = np.ascontiguousarray(codes[keep]), np.ascontiguousarray(out[keep])
+        if not len(k1):
+            k1 = cd = np.zeros(1, dtype=np.int64)
+        mid = c_int32()
+        ptr = ctypes.POINTER(c_int64)
+        _lib.call("capf_session_value_map", self.session._h, k1.ctypes.data_as(ptr), None, cd.ctypes.data_as(ptr),
+                  int(keep.sum()), byref(mid))
         return "\x01vmap:%d" % mid.value
 
     def withColumns(self, *columns, header=None, params=None):

@@ -746,6 +746,36 @@ capf_status capf_table_name_list(capf_table *t, int32_t n, const char *const *co
 capf_status capf_session_value_map(capf_session *s, const int64_t *keys, const int64_t *keys2, const int64_t *codes,
                                    int64_t n, int32_t *map_id);
 
+/* String functions with literal arguments (FlinkSQLExprMapper.scala:187-195)
+ * evaluated on the session's device string heap, the results interned on the
+ * device.  iarg0 / iarg1: SUBSTRING's 1-based `from` and `len` (UTF-16 units,
+ * Calcite's SUBSTRING; len >= 0).  lit0: the literal of CONCAT_L (literal + s)
+ * / CONCAT_R (s + literal), or REPLACE's search literal (non-empty, matched
+ * byte for byte, leftmost and non-overlapping); lit1: REPLACE's replacement —
+ * dictionary codes.  Unused arguments are ignored.                          */
+enum {
+  CAPF_STR_FN_UPPER = 0,
+  CAPF_STR_FN_LOWER = 1,
+  CAPF_STR_FN_TRIM = 2,   /* TRIM / LTRIM / RTRIM strip ' ' (0x20) only */
+  CAPF_STR_FN_LTRIM = 3,
+  CAPF_STR_FN_RTRIM = 4,
+  CAPF_STR_FN_SUBSTRING = 5,
+  CAPF_STR_FN_CONCAT_L = 6,
+  CAPF_STR_FN_CONCAT_R = 7,
+  CAPF_STR_FN_REPLACE = 8
+};
+/* out[i] (host, n entries) = the code of fn applied to dictionary string
+ * src[i] — or, src NULL, to string c0 + i (a range of the dictionary); −1 where
+ * src[i] is −1 (NULL); −2 where the caller must evaluate the function itself
+ * with the JVM's semantics: UPPER / LOWER of a string with a byte >= 0x80,
+ * SUBSTRING of a string with a supplementary character, REPLACE in a subject
+ * of at least CAPF_STR_LONG bytes.  Results new to the dictionary are appended
+ * to it with ascending codes in the order of the first i producing each, so
+ * equal dictionaries given equal calls stay equal.  IllegalArgument: an
+ * unknown fn, a code out of range, len < 0, an empty search literal.        */
+capf_status capf_string_fn_codes(capf_session *s, int32_t fn, int64_t iarg0, int64_t iarg1, int64_t lit0,
+                                 int64_t lit1, const int64_t *src, int64_t c0, int64_t n, int64_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -911,6 +911,20 @@ JNI(jint, sessionValueMap)(JNIEnv *env, jobject, jlong s, jlongArray keys, jlong
     return -1;
   return id;
 }
+// a string function of n dictionary strings on the device heap (capf_string_fn_codes):
+// src (null: the range c0 .. c0 + n) and out are direct buffers of n longs each
+JNI(void, stringFnCodes)(JNIEnv *env, jobject, jlong s, jint fn, jlong iarg0, jlong iarg1, jlong lit0, jlong lit1,
+                         jobject src, jlong c0, jlong n, jobject out) {
+  void *o = direct(env, out);
+  void *in = direct(env, src);
+  if (n < 0 || n > (INT64_MAX >> 3) || (n > 0 && !o) || (o && env->GetDirectBufferCapacity(out) < 8 * n) ||
+      (src && (!in || env->GetDirectBufferCapacity(src) < 8 * n))) {
+    illegal_argument(env, "stringFnCodes: src (when given) and out must be direct buffers of at least 8 * n bytes");
+    return;
+  }
+  fail(env, capf_string_fn_codes(S(s), fn, iarg0, iarg1, lit0, lit1, static_cast<const int64_t *>(in), c0, n,
+                                 static_cast<int64_t *>(o)));
+}
 // device → device
 JNI(void, sessionCopyDevice)(JNIEnv *env, jobject, jlong s, jlong dst, jlong src, jlong bytes) {
   fail(env, capf_session_copy(S(s), reinterpret_cast<void *>(dst), reinterpret_cast<const void *>(src), bytes, 3));

@@ -57,21 +57,55 @@ final class GpuCypherSession private (val device: Int, hipStream: Long)
 
   private val maps = scala.collection.mutable.HashMap.empty[Seq[Any], (Long, Array[Long], String)]
 
-  /** Program name of the session code map of string function `key` (CAPF_OP_STR_MAP,
-    * GpuStringFunctions.apply): the function applied to every dictionary string
-    * with the JVM's own String semantics, the results interned; extended in
-    * place when the dictionary has grown since (the shim's twin of
-    * table.py GpuSession.string_map). */
+  /** capf_string_fn_codes' (fn, iarg0, iarg1, lit0, lit1) for string function `key`, the literals
+    * interned; None: the JVM evaluates it for every string — `=~`, a search literal that is a regex,
+    * a negative length (the twin of expr.py device_string_fn). */
+  private def deviceFnArgs(key: Seq[Any]): Option[(Int, Long, Long, Long, Long)] = key match {
+    case Seq("upper") => Some((Native.StrFnUpper, 0L, 0L, -1L, -1L))
+    case Seq("lower") => Some((Native.StrFnLower, 0L, 0L, -1L, -1L))
+    case Seq("trim") => Some((Native.StrFnTrim, 0L, 0L, -1L, -1L))
+    case Seq("ltrim") => Some((Native.StrFnLTrim, 0L, 0L, -1L, -1L))
+    case Seq("rtrim") => Some((Native.StrFnRTrim, 0L, 0L, -1L, -1L))
+    case Seq("substring", from: Long, len: Long) if len >= 0 => Some((Native.StrFnSubstring, from, len, -1L, -1L))
+    case Seq("concat_l", lit: String) => Some((Native.StrFnConcatL, 0L, 0L, intern(lit), -1L))
+    case Seq("concat_r", lit: String) => Some((Native.StrFnConcatR, 0L, 0L, intern(lit), -1L))
+    case Seq("replace", search: String, replacement: String) if GpuStringFunctions.plainReplaceLiteral(search) =>
+      Some((Native.StrFnReplace, 0L, 0L, intern(search), intern(replacement)))
+    case _ => None
+  }
+
+  /** The codes string function `key` gives the dictionary strings c0 until c0 + n: one
+    * Native.stringFnCodes call over the device heap (results interned on the device), then
+    * GpuStringFunctions + intern for the strings it answers StrFnOnHost for — all of them when the
+    * device does not evaluate `key` (the twin of table.py GpuSession.string_fn_codes). */
+  private def stringFnCodes(key: Seq[Any], c0: Long, n: Long): Array[Long] = {
+    val out = Array.fill(n.toInt)(Native.StrFnOnHost)
+    deviceFnArgs(key).filter(_ => n > 0).foreach { case (fn, i0, i1, l0, l1) =>
+      val buf = java.nio.ByteBuffer.allocateDirect(8 * n.toInt).order(java.nio.ByteOrder.nativeOrder())
+      Native.guard(Native.stringFnCodes(handle, fn, i0, i1, l0, l1, null, c0, n, buf))
+      buf.asLongBuffer().get(out)
+    }
+    out.indices.foreach { i =>
+      if (out(i) == Native.StrFnOnHost)
+        out(i) = GpuStringFunctions(key, Native.stringLookup(handle, c0 + i)).map(intern).getOrElse(-1L)
+    }
+    out
+  }
+
+  /** Program name of the session code map of string function `key` (CAPF_OP_STR_MAP):
+    * the function applied to every dictionary string — on the device heap, and with the
+    * JVM's own String semantics (GpuStringFunctions.apply) where the device leaves a
+    * string to the host — the results interned; extended in place when the dictionary
+    * has grown since (the shim's twin of table.py GpuSession.string_map). */
   def stringMap(key: Seq[Any]): Option[String] = maps.synchronized {
+    val args = deviceFnArgs(key)  // (interns the literals before the dictionary is measured)
     val n = { val d = new Array[Long](2); Native.guard(Native.stringDigest(handle, d)); d(0) }
     if (n > GpuCypherSession.CodeMapMax) None  // a large dictionary: the caller's value map
     else maps.get(key) match {
       case Some((m, _, name)) if m >= n => Some(name)
       case prev =>
         val old = prev.map(_._2).getOrElse(Array.empty[Long])
-        val codes = old ++ (old.length.toLong until n).map { c =>
-          GpuStringFunctions(key, Native.stringLookup(handle, c)).map(intern).getOrElse(-1L)
-        }
+        val codes = old ++ stringFnCodes(key, old.length.toLong, n - old.length)
         val id = Native.guard(prev match {  // a grown map replaces its table in place (capf_session_code_map_extend)
           case Some((_, _, was)) => Native.sessionCodeMapExtend(handle, was.stripPrefix("\u0001map:").toInt, codes)
           case None => Native.sessionCodeMap(handle, codes)

@@ -23,6 +23,12 @@ object GpuStringFunctions {
     case other => throw new IllegalArgumentException(s"unknown string function $other")
   }
 
+  /** replace's search literal is a Java regex: true when it is non-empty and holds no
+    * metacharacter, so that it matches exactly its own text and the device may replace
+    * byte for byte (the twin of expr.py plain_replace_literal). */
+  def plainReplaceLiteral(search: String): Boolean =
+    search.nonEmpty && !search.exists(ch => "\\^$.|?*+()[]{}".indexOf(ch) >= 0)
+
   private def trimSpaces(s: String, leading: Boolean, trailing: Boolean): String = {
     var b = 0
     var e = s.length

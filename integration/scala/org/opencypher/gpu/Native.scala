@@ -64,6 +64,18 @@ object Native {
   final val StrMatchEndsWith = 1
   final val StrMatchContains = 2
 
+  // CAPF_STR_FN_* (capf_string_fn_codes) and its "evaluate on the host" answer
+  final val StrFnUpper = 0
+  final val StrFnLower = 1
+  final val StrFnTrim = 2
+  final val StrFnLTrim = 3
+  final val StrFnRTrim = 4
+  final val StrFnSubstring = 5
+  final val StrFnConcatL = 6
+  final val StrFnConcatR = 7
+  final val StrFnReplace = 8
+  final val StrFnOnHost = -2L
+
   /** Runs a native call, rethrowing its failure as the okapi exception of that kind
     * (okapi-api/.../impl/exception/InternalException.scala:36-65). */
   def guard[A](body: => A): A =
@@ -94,6 +106,11 @@ object Native {
   @native def stringIntern(session: Long, s: String): Long
   @native def stringLookup(session: Long, code: Long): String
   @native def stringDigest(session: Long, out: Array[Long]): Unit
+  /** capf_string_fn_codes: `fn` (StrFn*) of n dictionary strings on the device heap — the codes in `src`
+    * (a direct buffer of n longs), or the range c0 until c0 + n when src is null; out (a direct buffer of
+    * n longs) takes each result's code, -1 for NULL, StrFnOnHost where the JVM must evaluate it. */
+  @native def stringFnCodes(session: Long, fn: Int, iarg0: Long, iarg1: Long, lit0: Long, lit1: Long,
+                            src: ByteBuffer, c0: Long, n: Long, out: ByteBuffer): Unit
 
   // construction (CAPFTable.scala:76-83, CAPFRecords.scala:47-100, RelationalCypherRecords.scala:43-54)
   @native def tableFromHost(session: Long, names: Array[String], types: Array[Int], data: Array[ByteBuffer],
