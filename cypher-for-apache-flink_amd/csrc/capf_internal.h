@@ -177,7 +177,7 @@ enum Op : int32_t {
   OP_TO_BOOLEAN = CAPF_OP_TO_BOOLEAN, OP_IN_SET = CAPF_OP_IN_SET, OP_STR_MAP = CAPF_OP_STR_MAP,
   OP_VALUE_MAP = CAPF_OP_VALUE_MAP, OP_STR_TO_NUM = CAPF_OP_STR_TO_NUM, OP_RAND = CAPF_OP_RAND,
   OP_LIST_INDEX = CAPF_OP_LIST_INDEX, OP_STR_RANK = CAPF_OP_STR_RANK,
-  OP_STR_MATCH = CAPF_OP_STR_MATCH
+  OP_STR_MATCH = CAPF_OP_STR_MATCH, OP_IN_LIST = CAPF_OP_IN_LIST
 };
 // a program name that refers to a session literal set ("\x01set:<id>"), not a column
 inline bool is_literal_set_name(const std::string &nm) { return nm.size() > 5 && nm.compare(0, 5, "\x01set:") == 0; }
@@ -273,7 +273,7 @@ __device__ inline bool ft_load(const FtOperand &o, int64_t r, int64_t &val) {
 // ------------------------------------------------------------- plan nodes
 enum class Kind {
   Source, Select, Filter, Join, Union, Distinct, Group, WithColumns, OrderBy, Skip, Limit, Explode, NameList,
-  ListColumns
+  ListColumns, ListFn
 };
 
 struct AggSpec {
@@ -321,6 +321,9 @@ struct Node {
   // ListColumns (a list literal of per-row elements): the child's columns
   // name_cols, row i's list = (col0[i], ..., colk-1[i]) of element type list_elem
   Type list_elem = Type::Null;
+  // ListFn (capf_table_list_fn): list_fn over the child's columns name_cols
+  // (-1: an absent slice bound / step), element type list_elem
+  int32_t list_fn = 0;
 
   // memoised result
   std::mutex mu;
@@ -576,6 +579,9 @@ ColPtr name_list_column(Session *s, const Data &d, const std::vector<int> &cols,
 DataPtr explode_list(Session *s, const Data &d, int list_col);
 // LIST column whose row i is (d.cols[cols[0]][i], ..., d.cols[cols[k-1]][i]) (lists.hip)
 ColPtr list_from_columns(Session *s, const Data &d, const std::vector<int> &cols, Type elem);
+// slice / reverse / concat / range (capf_table_list_fn) over columns `cols` of d
+// (-1: absent); `elem` the result's element type.
+ColPtr list_fn_column(Session *s, const Data &d, int32_t fn, const std::vector<int> &cols, Type elem);
 // collect(arg) per group (lists.hip): a Type::List column of g.ngroups lists.
 ColPtr collect_lists(Session *s, const Grouping &g, int64_t nrows, const ColPtr &arg,
                      bool distinct);

@@ -1220,6 +1220,36 @@ __device__ Val run_program(const Instr *code, int ncode, const ColView *cols, in
         st[sp++] = (k < 0 || k >= len) ? mknull(cols[ev].type) : load_col(cols[ev], o0 + k);
         break;
       }
+      case OP_IN_LIST: {  // x IN cols[in.i] (LIST offsets); cols[(int)in.f] the element column (< 0: none)
+        Val x = st[--sp];
+        const ColView &c = cols[in.i];
+        const int ev = (int)in.f;
+        if (!c.data || (c.valid && !c.valid[r])) {  // a NULL list
+          st[sp++] = mknull(CAPF_TYPE_BOOL);
+          break;
+        }
+        const int64_t o0 = ((const int64_t *)c.data)[r], o1 = ((const int64_t *)c.data)[r + 1];
+        if (o1 <= o0) {  // the empty list: FALSE, for a NULL x too
+          st[sp++] = mkb(false);
+          break;
+        }
+        // NULL-typed elements, a NULL x, or element and x types that are never equal
+        const bool num = x.t == CAPF_TYPE_INT64 || x.t == CAPF_TYPE_FLOAT64;
+        if (ev < 0 || x.nul || x.t == CAPF_TYPE_NULL ||
+            !(cols[ev].type == x.t ||
+              (num && (cols[ev].type == CAPF_TYPE_INT64 || cols[ev].type == CAPF_TYPE_FLOAT64)))) {
+          st[sp++] = mknull(CAPF_TYPE_BOOL);
+          break;
+        }
+        bool hit = false, nul = false;
+        for (int64_t q = o0; q < o1 && !hit; ++q) {
+          const Val e = load_col(cols[ev], q);
+          if (e.nul) nul = true;
+          else hit = cmp_vals(e, x) == 0;
+        }
+        st[sp++] = hit ? mkb(true) : nul ? mknull(CAPF_TYPE_BOOL) : mkb(false);
+        break;
+      }
       case OP_TO_BOOLEAN: {  // cols[in.i] = the session's strings parsed as booleans
         Val a = st[--sp];
         if (a.nul || a.t == CAPF_TYPE_BOOL) {
@@ -1384,7 +1414,7 @@ static DeviceProgram upload_program(Session *s, const Program &p,
       break;
     }
   for (auto &in : code)
-    if (in.op == OP_LIST_INDEX) {  // the element column of the list as one more view (index in f)
+    if (in.op == OP_LIST_INDEX || in.op == OP_IN_LIST) {  // the element column of the list as one more view (index in f)
       int idx = -1;
       for (size_t k = 0; k < names.size(); ++k)
         if (names[k] == p.names[(size_t)in.i]) idx = (int)k;
@@ -1453,7 +1483,7 @@ static DeviceProgram upload_program(Session *s, const Program &p,
       case OP_AND: case OP_OR: case OP_COALESCE: depth -= (int)in.i - 1; break;
       case OP_NOT: case OP_IS_NULL: case OP_IS_NOT_NULL: case OP_NEG: case OP_TO_FLOAT:
       case OP_TO_INTEGER: case OP_STR_LEN: case OP_TO_BOOLEAN: case OP_IN_SET: case OP_STR_MAP:
-      case OP_STR_TO_NUM: case OP_LIST_INDEX: case OP_STR_RANK: break;
+      case OP_STR_TO_NUM: case OP_LIST_INDEX: case OP_STR_RANK: case OP_IN_LIST: break;
       case OP_IF: depth -= 2; break;
       case OP_STR_MATCH: depth -= 1; break;  // pattern and subject in, a BOOLEAN out
       case OP_VALUE_MAP: depth -= in.f != 0.0 ? 1 : 0; break;

@@ -406,4 +406,264 @@ ColPtr list_from_columns(Session *s, const Data &d, const std::vector<int> &cols
   return list_column(s, n, off, child);
 }
 
+// ----------------------------------------------------------- list functions
+// slice / reverse / concat / range (capf_table_list_fn; okapi Expr.scala
+// :640-653, 859-880, 1166-1176; the Morpheus lowering SparkSQLExprMapper.scala
+// :171-182, 265, 269, 336-338).  Two launches around one exclusive scan:
+//   k_lfn_lengths: one thread per row → the row's result length (and, for a
+//     slice, its first source element), the row validity when some input can
+//     make the row NULL, the two range errors ORed into a flag word;
+//   k_lfn_fill: one thread per OUTPUT ELEMENT, so a list of any length is
+//     spread over lanes and blocks.  A block owns 256 consecutive output
+//     elements per grid-stride step; waves 0 and 1 find the rows of the tile's
+//     first and last element (the last r with off[r] <= o, an upper bound over
+//     the new offsets, which steps over runs of empty rows; 64 probes per
+//     round) and leave that row window in LDS; every thread then searches only
+//     inside the window.
+// Sources are read through ColView (ld_int), so an encoded column stays
+// correct; stores are contiguous, 8 B per lane (1 B for BOOLEAN).
+struct ListSide {
+  const int64_t *off;    // LIST side: its offsets [n + 1]; null: a scalar side (or absent)
+  const uint8_t *valid;  // LIST side: the list validity (may be null)
+  ColView e;             // LIST side: the element column; scalar side: the column itself
+};
+struct ListFnArgs {
+  int32_t fn;
+  int32_t elem;  // the result's element type
+  ListSide a, b;
+  ColView p[3];  // SLICE: p[0] from, p[1] to; RANGE: from, to, step
+  int32_t has[3];
+};
+
+constexpr uint32_t LFN_ERR_STEP0 = 1, LFN_ERR_LONG = 2;
+constexpr int64_t LFN_MAX_LEN = 2147483647;  // Spark's sequence / array limit
+
+// INTEGER argument at row r (false: NULL)
+__device__ inline bool lfn_arg(const ColView &c, int64_t r, int64_t &v) {
+  if (c.type == CAPF_TYPE_NULL || !c.data || (c.valid && !c.valid[r])) return false;
+  v = ld_int(c, r);
+  return true;
+}
+
+// a slice bound against a list of len elements: from the end when negative, clamped
+__device__ inline int64_t lfn_bound(int64_t x, int64_t len) {
+  if (x < 0) return x < -len ? 0 : x + len;
+  return x > len ? len : x;
+}
+
+__global__ void k_lfn_lengths(ListFnArgs g, int64_t n, int64_t *len, int64_t *first, uint8_t *valid,
+                              uint32_t *err) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
+    bool ok = true;
+    int64_t k = 0;
+    if (g.fn == CAPF_LIST_FN_RANGE) {
+      int64_t a = 0, b = 0, st = 1;
+      ok = lfn_arg(g.p[0], r, a) && lfn_arg(g.p[1], r, b) && (!g.has[2] || lfn_arg(g.p[2], r, st));
+      if (ok && st == 0) {
+        atomicOr(err, LFN_ERR_STEP0);
+      } else if (ok && (st > 0 ? b >= a : b <= a)) {
+        // the distance and the step as unsigned 64-bit values: neither wraps
+        const uint64_t dist = st > 0 ? (uint64_t)b - (uint64_t)a : (uint64_t)a - (uint64_t)b;
+        const uint64_t us = st > 0 ? (uint64_t)st : 0 - (uint64_t)st;
+        const uint64_t q = dist / us;  // the index of the last element
+        if (q >= (uint64_t)LFN_MAX_LEN) atomicOr(err, LFN_ERR_LONG);
+        else k = (int64_t)q + 1;
+      }
+    } else {
+      const bool al = g.a.off != nullptr, bl = g.b.off != nullptr;
+      if (al && g.a.valid && !g.a.valid[r]) ok = false;
+      if (bl && g.b.valid && !g.b.valid[r]) ok = false;
+      const int64_t la = al ? g.a.off[r + 1] - g.a.off[r] : 1;
+      if (g.fn == CAPF_LIST_FN_REVERSE) {
+        k = la;
+      } else if (g.fn == CAPF_LIST_FN_CONCAT) {
+        k = la + (bl ? g.b.off[r + 1] - g.b.off[r] : 1);
+      } else {  // SLICE: an empty list, like a NULL bound, gives NULL
+        int64_t lo = 0, hi = la;
+        if (la == 0 || (g.has[0] && !lfn_arg(g.p[0], r, lo)) || (g.has[1] && !lfn_arg(g.p[1], r, hi))) ok = false;
+        lo = lfn_bound(lo, la);
+        hi = lfn_bound(hi, la);
+        k = hi > lo ? hi - lo : 0;
+        first[r] = lo;
+      }
+    }
+    len[r] = ok ? k : 0;
+    if (valid) valid[r] = ok ? 1 : 0;
+  }
+}
+
+// element i of source view c as the result's element type into slot d
+__device__ inline void lfn_store(const ColView &c, int64_t i, int32_t elem, void *child, uint8_t *cvalid, int64_t d) {
+  const bool ok = c.type != CAPF_TYPE_NULL && c.data && !(c.valid && !c.valid[i]);
+  if (elem == CAPF_TYPE_BOOL) {
+    ((uint8_t *)child)[d] = ok && ((const uint8_t *)c.data)[i] ? 1 : 0;
+  } else if (elem == CAPF_TYPE_FLOAT64) {
+    ((double *)child)[d] = !ok ? 0.0 : c.type == CAPF_TYPE_FLOAT64 ? ((const double *)c.data)[i] : (double)ld_int(c, i);
+  } else {
+    ((int64_t *)child)[d] = ok ? ld_int(c, i) : 0;
+  }
+  if (cvalid) cvalid[d] = ok ? 1 : 0;
+}
+
+// the last r in [lo, hi] with off[r] <= o (off[lo] <= o holds)
+__device__ inline int64_t lfn_row_of(const int64_t *off, int64_t lo, int64_t hi, int64_t o) {
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo + 1) / 2;
+    if (off[mid] <= o) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// The same over [0, n - 1] by one whole wave, 64 probes per round (lane = the
+// caller's lane; every lane returns the row): a tile's first and last rows
+// cost log64(n) dependent loads instead of log2(n).  The offsets ascend, so
+// the probes that hold are a prefix of the lanes and their count is the answer.
+__device__ inline int64_t lfn_row_of_wave(const int64_t *off, int64_t n, int64_t o, int lane) {
+  int64_t lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int64_t step = (hi - lo + 63) / 64;  // the candidates lo + 1 .. hi in 64 runs of `step`
+    const int64_t idx = lo + 1 + (int64_t)lane * step;
+    const bool le = idx <= hi && off[idx] <= o;
+    const int c = __popcll(__ballot(le));
+    if (c == 0) {
+      hi = lo;
+    } else {
+      lo += 1 + (int64_t)(c - 1) * step;
+      hi = lo + step - 1 < hi ? lo + step - 1 : hi;
+    }
+  }
+  return lo;
+}
+
+constexpr int LFN_BLOCK = 256;
+
+// off: the result's offsets [n + 1], off[n] = total > 0
+__global__ __launch_bounds__(LFN_BLOCK) void k_lfn_fill(ListFnArgs g, int64_t n, const int64_t *off, int64_t total,
+                                                        const int64_t *first, void *child, uint8_t *cvalid) {
+  __shared__ int64_t s_win[2];
+  for (int64_t o0 = (int64_t)blockIdx.x * LFN_BLOCK; o0 < total; o0 += (int64_t)gridDim.x * LFN_BLOCK) {
+    if (threadIdx.x < 128) {  // waves 0 and 1: the rows of the tile's first and last element
+      const int64_t last = o0 + LFN_BLOCK - 1 < total ? o0 + LFN_BLOCK - 1 : total - 1;
+      const int w = threadIdx.x >> 6;
+      const int64_t r = lfn_row_of_wave(off, n, w ? last : o0, threadIdx.x & 63);
+      if ((threadIdx.x & 63) == 0) s_win[w] = r;
+    }
+    __syncthreads();
+    const int64_t o = o0 + threadIdx.x;
+    if (o < total) {
+      const int64_t r = lfn_row_of(off, s_win[0], s_win[1], o);
+      const int64_t q = o - off[r];
+      if (g.fn == CAPF_LIST_FN_RANGE) {
+        int64_t a = 0, st = 1;
+        lfn_arg(g.p[0], r, a);
+        if (g.has[2]) lfn_arg(g.p[2], r, st);
+        // a + q·st lies between from and to: the unsigned sum is that value
+        ((int64_t *)child)[o] = (int64_t)((uint64_t)a + (uint64_t)q * (uint64_t)st);
+      } else if (g.fn == CAPF_LIST_FN_SLICE) {
+        lfn_store(g.a.e, g.a.off[r] + first[r] + q, g.elem, child, cvalid, o);
+      } else if (g.fn == CAPF_LIST_FN_REVERSE) {
+        lfn_store(g.a.e, g.a.off[r] + (off[r + 1] - off[r]) - 1 - q, g.elem, child, cvalid, o);
+      } else {  // CONCAT: side A's elements, then side B's; a scalar side reads the row's value
+        const int64_t la = g.a.off ? g.a.off[r + 1] - g.a.off[r] : 1;
+        if (q < la) lfn_store(g.a.e, g.a.off ? g.a.off[r] + q : r, g.elem, child, cvalid, o);
+        else lfn_store(g.b.e, g.b.off ? g.b.off[r] + (q - la) : r, g.elem, child, cvalid, o);
+      }
+    }
+    __syncthreads();  // (the window is rewritten by the next step)
+  }
+}
+
+static const ColView LFN_NO_COL{nullptr, nullptr, CAPF_TYPE_NULL, ENC_PLAIN, 0};
+
+// One side of SLICE / REVERSE / CONCAT as kernel arguments; `nullable`: the
+// side can give a NULL element, `row_null`: it can make the row NULL.
+static ListSide list_side(const ColPtr &c, bool &nullable, bool &row_null) {
+  ListSide sd{nullptr, nullptr, LFN_NO_COL};
+  if (c->type == Type::List) {
+    force(c);
+    sd.off = c->data ? (const int64_t *)c->data->p : nullptr;  // (null only without rows: nothing launches)
+    sd.valid = c->valid ? (const uint8_t *)c->valid->p : nullptr;
+    row_null = row_null || c->valid;
+    if (c->child && c->child->type != Type::Null) {
+      sd.e = view_of(c->child);
+      nullable = nullable || c->child->valid;
+    } else {
+      nullable = true;  // NULL-typed elements
+    }
+  } else if (c->type == Type::Null) {  // a NULL scalar: one NULL element
+    nullable = true;
+  } else {
+    sd.e = view_of(c);
+    nullable = nullable || c->valid;
+  }
+  return sd;
+}
+
+ColPtr list_fn_column(Session *s, const Data &d, int32_t fn, const std::vector<int> &cols, Type elem) {
+  const int64_t n = d.nrows;
+  auto arg = [&](size_t j) -> ColPtr { return j < cols.size() && cols[j] >= 0 ? d.cols[(size_t)cols[j]] : nullptr; };
+  ListFnArgs g{};
+  g.fn = fn;
+  g.elem = (int32_t)elem;
+  g.a = g.b = ListSide{nullptr, nullptr, LFN_NO_COL};
+  for (auto &v : g.p) v = LFN_NO_COL;
+  bool nullable = false, row_null = false;
+  if (fn == CAPF_LIST_FN_RANGE) {
+    for (size_t j = 0; j < 3; ++j)
+      if (ColPtr c = arg(j)) {
+        g.has[j] = 1;
+        if (c->type != Type::Null) g.p[j] = view_of(c);
+        row_null = row_null || c->type == Type::Null || c->valid;
+      }
+  } else {
+    g.a = list_side(arg(0), nullable, row_null);
+    if (fn == CAPF_LIST_FN_CONCAT) g.b = list_side(arg(1), nullable, row_null);
+    if (fn == CAPF_LIST_FN_SLICE) {
+      row_null = true;  // an empty list gives NULL
+      for (size_t j = 1; j < 3; ++j)
+        if (ColPtr c = arg(j)) {
+          g.has[j - 1] = 1;
+          if (c->type != Type::Null) g.p[j - 1] = view_of(c);
+        }
+    }
+  }
+  BufPtr off = s->alloc(8 * (n + 1));
+  HIP_CHECK(hipMemsetAsync(off->p, 0, 8 * (n + 1), s->stream));
+  if (n == 0) return list_column(s, 0, off, empty_elements(s, elem));
+  BufPtr len = s->alloc(8 * (n + 1));  // len[n] = 0: the scan's last entry is the element total
+  HIP_CHECK(hipMemsetAsync(len->p, 0, 8 * (n + 1), s->stream));
+  BufPtr first = fn == CAPF_LIST_FN_SLICE ? s->alloc(8 * n) : nullptr;
+  BufPtr valid = row_null ? s->alloc(n) : nullptr;
+  BufPtr err = fn == CAPF_LIST_FN_RANGE ? s->alloc(8) : nullptr;
+  if (err) HIP_CHECK(hipMemsetAsync(err->p, 0, 8, s->stream));
+  hipLaunchKernelGGL(k_lfn_lengths, dim3(grid_for(n, 256)), dim3(256), 0, s->stream, g, n, (int64_t *)len->p,
+                     first ? (int64_t *)first->p : nullptr, valid ? (uint8_t *)valid->p : nullptr,
+                     err ? (uint32_t *)err->p : nullptr);
+  KERNEL_CHECK();
+  const int64_t total = exclusive_scan_i64(s, (const int64_t *)len->p, (int64_t *)off->p, n + 1);
+  if (err) {  // (the scan has synchronised the stream)
+    uint32_t e = 0;
+    HIP_CHECK(hipMemcpyAsync(&e, err->p, 4, hipMemcpyDeviceToHost, s->stream));
+    s->sync();
+    if (e & LFN_ERR_STEP0) illegal("range() with a step of 0");
+    if (e & LFN_ERR_LONG) illegal("range() of more than 2147483647 elements");
+  }
+  ColPtr child;
+  if (total == 0) {
+    child = empty_elements(s, elem);
+  } else if (elem == Type::Null) {  // NULL-typed elements move no bytes
+    child = null_column(s, Type::Null, total);
+  } else {
+    child = make_column(s, elem, total, nullable);
+    hipLaunchKernelGGL(k_lfn_fill, dim3(grid_for(total, LFN_BLOCK)), dim3(LFN_BLOCK), 0, s->stream, g, n,
+                       (const int64_t *)off->p, total, first ? (const int64_t *)first->p : nullptr,
+                       child->data->p, child->valid ? (uint8_t *)child->valid->p : nullptr);
+    KERNEL_CHECK();
+  }
+  ColPtr o = list_column(s, n, off, child);
+  o->valid = valid;
+  return o;
+}
+
 }  // namespace capf

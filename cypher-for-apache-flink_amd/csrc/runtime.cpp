@@ -201,7 +201,8 @@ Program Program::from_c(const capf_expr *e) {
 std::vector<std::string> Program::referenced() const {
   std::vector<std::string> r;
   for (auto &in : code)
-    if (in.op == OP_COL || in.op == OP_LIST_SIZE || in.op == OP_LIST_INDEX) r.push_back(names[in.i]);
+    if (in.op == OP_COL || in.op == OP_LIST_SIZE || in.op == OP_LIST_INDEX || in.op == OP_IN_LIST)
+      r.push_back(names[in.i]);
   return r;
 }
 
@@ -415,6 +416,20 @@ Type infer_type(const Program &p, const std::vector<std::string> &names,
         const int et = (int)in.f;
         if (et < 0 || et > 4) illegal("list element type out of range");
         st.push_back((Type)et);
+        break;
+      }
+      case OP_IN_LIST: {
+        if (in.i < 0 || (size_t)in.i >= p.names.size()) illegal("malformed expression program (column)");
+        const std::string &nm = p.names[in.i];
+        int idx = -1;
+        for (size_t k = 0; k < names.size(); ++k)
+          if (names[k] == nm) idx = (int)k;
+        if (idx < 0) illegal("expression references unknown column '" + nm + "'");
+        if (types[idx] != Type::List && types[idx] != Type::Null) illegal("IN over a non-list column");
+        const int et = (int)in.f;
+        if (et < 0 || et > 4) illegal("list element type out of range");
+        pop();
+        st.push_back(Type::Bool);
         break;
       }
       default: not_impl("expression opcode " + std::to_string(in.op));
@@ -681,6 +696,16 @@ static DataPtr materialize_impl(const NodePtr &n) {
       out->nrows = c->nrows;
       out->cols = c->cols;
       out->cols.push_back(list_from_columns(s, *c, n->name_cols, n->list_elem));
+      return out;
+    }
+    case Kind::ListFn: {
+      DataPtr c = materialize(n->kids[0]);
+      auto out = std::make_shared<Data>();
+      out->nrows = c->nrows;
+      out->cols = c->cols;
+      out->cols.push_back(n->types.back() == Type::Null
+                              ? null_column(s, Type::Null, c->nrows)
+                              : list_fn_column(s, *c, n->list_fn, n->name_cols, n->list_elem));
       return out;
     }
     case Kind::WithColumns: {
@@ -1965,6 +1990,7 @@ static bool static_list_elem(const NodePtr &n, int i, Type &et, int depth = 0) {
       et = Type::String;
       return true;
     case Kind::ListColumns:
+    case Kind::ListFn:
       if (i < nk) return static_list_elem(n->kids[0], i, et, depth + 1);
       et = n->list_elem;
       return true;
@@ -2547,6 +2573,79 @@ capf_status capf_table_list_columns(capf_table *t, int32_t n, const char *const 
   nn->list_elem = et;
   nn->names.emplace_back(name);
   nn->types.push_back(Type::List);
+  *out = wrap(nn);
+  CAPF_API_END
+}
+
+// Element type of LIST column i of node c: off the plan, else by evaluating it.
+static Type list_elem_of(const NodePtr &c, int i) {
+  Type et;
+  if (static_list_elem(c, i, et)) return et;
+  DataPtr d = materialize(c);
+  const ColPtr &lc = d->cols[(size_t)i];
+  return lc->child ? lc->child->type : Type::Null;
+}
+
+capf_status capf_table_list_fn(capf_table *t, int32_t fn, int32_t nargs, const char *const *args,
+                               const char *name, capf_table **out) {
+  CAPF_API_BEGIN
+  need(t, "table");
+  need(name, "name");
+  need(out, "out");
+  static const int32_t want[4] = {3, 1, 2, 3};
+  if (fn < CAPF_LIST_FN_SLICE || fn > CAPF_LIST_FN_RANGE) illegal("unknown list function");
+  if (nargs != want[fn] || !args) illegal("wrong number of list function arguments");
+  const NodePtr &c = t->node;
+  if (c->col_index(name) >= 0) illegal(std::string("column '") + name + "' already exists");
+  auto nn = new_node(c->s, Kind::ListFn);
+  nn->kids.push_back(c);
+  nn->names = c->names;
+  nn->types = c->types;
+  nn->list_fn = fn;
+  for (int32_t j = 0; j < nargs; ++j) {
+    need(args[j], "args[j]");
+    const bool optional = (fn == CAPF_LIST_FN_SLICE && j > 0) || (fn == CAPF_LIST_FN_RANGE && j == 2);
+    if (!args[j][0] && !optional) illegal("a list function argument is missing");
+    nn->name_cols.push_back(args[j][0] ? c->col_index_or_throw(args[j]) : -1);
+  }
+  auto type_of = [&](int j) { return c->types[(size_t)nn->name_cols[(size_t)j]]; };
+  auto integer_arg = [&](int j, const char *what) {
+    if (nn->name_cols[(size_t)j] >= 0 && type_of(j) != Type::Int64 && type_of(j) != Type::Null)
+      illegal(std::string(what) + " must be an INTEGER, got " + type_name(type_of(j)));
+  };
+  Type out_type = Type::List;
+  if (fn == CAPF_LIST_FN_RANGE) {
+    for (int j = 0; j < 3; ++j) integer_arg(j, "a range() argument");
+    nn->list_elem = Type::Int64;
+  } else if (fn == CAPF_LIST_FN_CONCAT) {
+    if (type_of(0) != Type::List && type_of(1) != Type::List) illegal("list concatenation without a list side");
+    Type et = Type::Null;
+    for (int j = 0; j < 2; ++j) {
+      const Type ct = type_of(j) == Type::List ? list_elem_of(c, nn->name_cols[(size_t)j]) : type_of(j);
+      if (ct == Type::List) not_impl("nested lists");
+      if (ct == Type::Null || et == Type::Null || et == ct) et = ct == Type::Null ? et : ct;
+      else if ((et == Type::Int64 || et == Type::Float64) && (ct == Type::Int64 || ct == Type::Float64))
+        et = Type::Float64;  // INTEGER and FLOAT elements widen together
+      else
+        not_impl(std::string("Lists of different inner types are not supported (") + type_name(et) + ", " +
+                 type_name(ct) + ")");
+    }
+    nn->list_elem = et;
+  } else {  // SLICE / REVERSE
+    if (type_of(0) == Type::Null) {
+      out_type = Type::Null;  // a NULL list
+    } else if (type_of(0) != Type::List) {
+      not_impl(std::string(fn == CAPF_LIST_FN_SLICE ? "a slice" : "reverse()") + " of a " + type_name(type_of(0)));
+    } else {
+      nn->list_elem = list_elem_of(c, nn->name_cols[0]);
+    }
+    if (fn == CAPF_LIST_FN_SLICE) {
+      integer_arg(1, "a slice bound");
+      integer_arg(2, "a slice bound");
+    }
+  }
+  nn->names.emplace_back(name);
+  nn->types.push_back(out_type);
   *out = wrap(nn);
   CAPF_API_END
 }

@@ -39,7 +39,7 @@ OP_STR_LEN, OP_LIST_SIZE, OP_IF = 60, 61, 62
 OP_ROUND, OP_ABS, OP_CEIL, OP_FLOOR, OP_SIGN, OP_SQRT, OP_LOG, OP_LOG10, OP_EXP = 70, 71, 72, 73, 74, 75, 76, 77, 78
 OP_SIN, OP_COS, OP_TAN, OP_ASIN, OP_ACOS, OP_ATAN, OP_DEGREES, OP_RADIANS = 79, 80, 81, 82, 83, 84, 85, 86
 OP_ATAN2, OP_TO_BOOLEAN, OP_IN_SET, OP_STR_MAP, OP_VALUE_MAP = 87, 88, 89, 90, 91
-OP_STR_TO_NUM, OP_RAND, OP_LIST_INDEX, OP_STR_RANK, OP_STR_MATCH = 92, 93, 94, 95, 96
+OP_STR_TO_NUM, OP_RAND, OP_LIST_INDEX, OP_STR_RANK, OP_STR_MATCH, OP_IN_LIST = 92, 93, 94, 95, 96, 97
 IN_SET_MIN = 17  # list length from which IN runs as a session-set lookup (shorter: an OR of equalities)
 
 # aggregators
@@ -258,9 +258,18 @@ class ListLit(Expr):
 
 @dataclass(frozen=True)
 class In(Expr):
-    """lhs IN rhs (okapi In; FlinkSQLExprMapper.scala:114-118): rhs a list
-    literal or a list parameter.  SQL IN semantics: NULL when lhs is NULL or
-    when nothing matches and the list holds a NULL; an empty list is FALSE."""
+    """lhs IN rhs (okapi In; FlinkSQLExprMapper.scala:114-118).  SQL IN
+    semantics: NULL when lhs is NULL or when nothing matches and the list
+    holds a NULL; an empty list is FALSE.  rhs a list literal or a list
+    parameter folds into equalities / a session set; rhs a LIST column — or any
+    per-row list expression, which the table operations project to one first
+    (table.py `_hoist_lists`) — is CAPF_OP_IN_LIST (Morpheus array_contains,
+    SparkSQLExprMapper.scala:161-164), in this order: a NULL list gives NULL;
+    an empty list FALSE, for a NULL lhs too (NullTests.scala:127); a NULL lhs
+    NULL; a non-NULL element equal to lhs (CAPF_OP_EQ's equality) TRUE;
+    otherwise NULL when the list holds a NULL element, else FALSE
+    (NullTests.scala:128-132); an element type that can never equal the type
+    of lhs gives NULL, as `_comparable` decides for literals."""
     lhs: Expr
     rhs: Expr
 
@@ -533,6 +542,142 @@ class ContainerIndex(Expr):
 
     def __str__(self):
         return f"{self.container}[{self.index}]"
+
+
+# List functions (okapi Expr.scala:640-653 Head / Last / Reverse, :859-880
+# Range, :1166-1176 ListSliceFromTo / ListSliceFrom / ListSliceTo).  Flink's
+# mapper lowers none of them; the semantics are the Morpheus lowering
+# (SparkSQLExprMapper.scala:161-168, 171-182, 265, 269, 336-338,
+# MorpheusFunctions.scala:79-83) with the shared expectations
+# (FunctionTests.scala:1502-1556, 1631-1718, ExpressionTests.scala:47-80,
+# NullTests.scala:55-57, 63, 107).
+# head(xs) / last(xs): xs[0] / xs[-1] (element_at(xs, 1 / -1), :167-168) —
+# CAPF_OP_LIST_INDEX; a literal list folds; an empty or NULL list gives NULL.
+Head = _unary("Head", "head({})")
+Last = _unary("Last", "last({})")
+# reverse(xs) (:265): the elements in reverse order, NULL elements included; a
+# NULL list gives NULL.  reverse of a STRING (and split) is NotImplemented.
+Reverse = _unary("Reverse", "reverse({})")
+
+
+@dataclass(frozen=True)
+class Range(Expr):
+    """range(frm, to[, step]) (okapi Range, Expr.scala:859-880; Spark
+    sequence, SparkSQLExprMapper.scala:269): INTEGER arguments, step 1 when
+    absent, the end inclusive — list(range(a, b + 1, s)) for s > 0,
+    list(range(a, b - 1, s)) for s < 0; a direction that never arrives is the
+    empty list; a NULL argument gives a NULL list (NullTests.scala:107).  A
+    step of 0, or a row of more than 2^31 − 1 elements (Spark's limit), is an
+    IllegalArgumentException when the plan executes."""
+    frm: Expr
+    to: Expr
+    step: Expr = None
+
+    def __str__(self):
+        return f"range({self.frm}, {self.to}" + (f", {self.step})" if self.step is not None else ")")
+
+
+@dataclass(frozen=True)
+class ListSliceFromTo(Expr):
+    """list[frm..to] (okapi ListSliceFromTo, Expr.scala:1166-1176; Morpheus
+    list_slice, SparkSQLExprMapper.scala:336-338, MorpheusFunctions.scala:79-83):
+    Python's xs[frm:to] — bounds from the end when negative, clamped to the
+    list, empty when frm >= to (Cypher's answers, not Spark slice's errors, as
+    ContainerIndex decided for indexing).  An EMPTY list gives NULL, not []
+    (ExpressionTests.scala:70-79, FunctionTests.scala:1665-1674); so does a
+    NULL list or a NULL bound.  tail(xs) is ListSliceFrom(xs, 1)."""
+    list: Expr
+    frm: Expr
+    to: Expr
+
+    def __str__(self):
+        return f"{self.list}[{self.frm}..{self.to}]"
+
+
+@dataclass(frozen=True)
+class ListSliceFrom(Expr):
+    """list[frm..] (see ListSliceFromTo)."""
+    list: Expr
+    frm: Expr
+
+    def __str__(self):
+        return f"{self.list}[{self.frm}..]"
+
+
+@dataclass(frozen=True)
+class ListSliceTo(Expr):
+    """list[..to] (see ListSliceFromTo)."""
+    list: Expr
+    to: Expr
+
+    def __str__(self):
+        return f"{self.list}[..{self.to}]"
+
+
+LIST_FN_SLICE, LIST_FN_REVERSE, LIST_FN_CONCAT, LIST_FN_RANGE = 0, 1, 2, 3  # CAPF_LIST_FN_*
+
+
+def list_fn_args(e):
+    """(CAPF_LIST_FN_* selector, argument expressions; None = absent) of a
+    list-valued function expression — Reverse, Range, a slice, or an Add that
+    concatenates lists (xs + ys, xs + x, x + xs: SparkSQLExprMapper.scala:
+    171-182; a scalar side is a one-element list)."""
+    if isinstance(e, Reverse):
+        return LIST_FN_REVERSE, (e.expr,)
+    if isinstance(e, Range):
+        return LIST_FN_RANGE, (e.frm, e.to, e.step)
+    if isinstance(e, ListSliceFromTo):
+        return LIST_FN_SLICE, (e.list, e.frm, e.to)
+    if isinstance(e, ListSliceFrom):
+        return LIST_FN_SLICE, (e.list, e.frm, None)
+    if isinstance(e, ListSliceTo):
+        return LIST_FN_SLICE, (e.list, None, e.to)
+    if type(e).__name__ == "Add":
+        return LIST_FN_CONCAT, (e.lhs, e.rhs)
+    return None
+
+
+def sub_exprs(e):
+    """The direct sub-expressions of e (a list literal's items are not
+    descended into: nested lists are not supported)."""
+    if isinstance(e, (Var, ElementProperty)):
+        return []
+    if isinstance(e, CaseExpr):
+        out = [x for pv in e.alternatives for x in pv]
+        return out + ([e.default] if e.default is not None else [])
+    if isinstance(e, (Ands, Ors, Coalesce)):
+        return list(e.exprs)
+    names = _FIELD_NAMES.get(type(e))
+    if names is None:
+        import dataclasses
+        names = _FIELD_NAMES[type(e)] = tuple(f.name for f in dataclasses.fields(e)) \
+            if dataclasses.is_dataclass(e) else ()
+    return [x for x in (getattr(e, nm) for nm in names) if isinstance(x, Expr)]
+
+
+_FIELD_NAMES = {}  # dataclass field names per expression class
+
+
+def may_hold_list_fn(e):
+    """Could some sub-expression of e be list-valued (list_valued, or a list
+    literal below the top)?  Structural, so kept on the instance: the table
+    operations ask it of every expression they lower."""
+    try:
+        return e.__dict__["_lf"]
+    except KeyError:
+        k = e.__dict__["_lf"] = (isinstance(e, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo))
+                                 or type(e).__name__ == "Add"
+                                 or any(isinstance(x, ListLit) or may_hold_list_fn(x) for x in sub_exprs(e)))
+        return k
+
+
+def list_valued(e, header, columns, params=None, coltype=None):
+    """Is e a list-valued expression the table operations project to a
+    temporary LIST column before the rest is lowered: Reverse, Range, a slice,
+    or an Add whose static type is LIST."""
+    if isinstance(e, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo)):
+        return True
+    return type(e).__name__ == "Add" and _static_type(e, header, columns, params, coltype) == T_LIST
 
 
 @dataclass(frozen=True)
@@ -947,6 +1092,72 @@ def compile_program(expr, header, columns, params=None, intern=None, coltype=Non
     return prog
 
 
+def _static_type(e, header, columns, params=None, coltype=None):
+    """capf type of e when known without evaluating it, else None."""
+    c = resolve_column(e, header, columns) if header is not None and e in header else None
+    if c is not None:
+        return coltype(c) if coltype is not None else CT_TO_CAPF.get(getattr(e, "ctype", "ANY"))
+    if isinstance(e, (IntegerLit, FloatLit, StringLit, BoolLit)):
+        return _value_type(e.v)
+    if isinstance(e, NullLit):
+        return T_NULL
+    if isinstance(e, Param):
+        return _value_type((params or {}).get(e.pname))
+    if isinstance(e, (Var, ElementProperty)):  # no column: a NULL literal
+        return T_NULL
+    if isinstance(e, (ToFloat,)) or type(e).__name__ in _FLOAT_FUNCS or isinstance(e, (E_, Pi_, Rand_)):
+        return T_FLOAT
+    if type(e).__name__ in ("Labels", "Keys") and isinstance(e.expr, NullLit):
+        return T_NULL
+    if isinstance(e, (ToInteger, Size, Id)):
+        return T_INT
+    if isinstance(e, ToBoolean) or type(e).__name__ == "RegexMatch" or type(e).__name__ in _STR_MATCH:
+        return T_BOOL
+    if type(e).__name__ in _STR_FUNCS or isinstance(e, (Substring, Replace, ToString)):
+        return T_STRING
+    if isinstance(e, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo)):
+        return T_LIST
+    if isinstance(e, (Head, Last)):  # the element type where the column type is known
+        x = e.expr
+        vals = list_values(x, params) if isinstance(x, (ListLit, Param)) else None
+        if vals is not None:
+            kinds = {_value_type(v) for v in vals if v is not None}
+            return (T_NULL if not kinds else T_FLOAT if kinds == {T_INT, T_FLOAT} else
+                    kinds.pop() if len(kinds) == 1 else None)
+        cx = resolve_column(x, header, columns) if header is not None and x in header else None
+        if cx is not None and coltype is not None:
+            return coltype(("elem", cx)) if coltype(cx) == T_LIST else T_NULL if coltype(cx) == T_NULL else None
+        return T_NULL if isinstance(x, NullLit) else None
+    name = type(e).__name__
+    if name == "Add":  # a list side: concatenation
+        for x in (e.lhs, e.rhs):
+            if isinstance(x, ListLit) or (isinstance(x, Param) and isinstance((params or {}).get(x.pname), (list, tuple))) \
+                    or _static_type(x, header, columns, params, coltype) == T_LIST:
+                return T_LIST
+    if name in ("Add", "Subtract", "Multiply", "Divide", "Modulo"):
+        ta, tb = _static_type(e.lhs, header, columns, params, coltype), _static_type(e.rhs, header, columns, params, coltype)
+        if name == "Add" and T_STRING in (ta, tb):
+            return T_STRING
+        if ta in (T_INT, T_FLOAT) and tb in (T_INT, T_FLOAT):
+            return T_FLOAT if T_FLOAT in (ta, tb) else T_INT
+        return None
+    if name in ("Negate", "Abs", "Ceil", "Floor", "Sign"):
+        t = _static_type(e.expr, header, columns, params, coltype)
+        return t if t in (T_INT, T_FLOAT) else None
+    if name in _CMP_NAMES or isinstance(e, (Ands, Ors, In)) or name in ("Not", "IsNull", "IsNotNull", "Exists"):
+        return T_BOOL
+    if isinstance(e, (Coalesce, CaseExpr)):  # the branches' common type (INTEGER and FLOAT: FLOAT)
+        parts = list(e.exprs) if isinstance(e, Coalesce) else \
+            [v for _, v in e.alternatives] + ([e.default] if e.default is not None else [])
+        ts = {_static_type(x, header, columns, params, coltype) for x in parts} - {T_NULL}
+        if None in ts or not ts:
+            return None if None in ts else T_NULL
+        if ts == {T_INT, T_FLOAT}:
+            return T_FLOAT
+        return ts.pop() if len(ts) == 1 else None
+    return None
+
+
 def _compile_program(expr, header, columns, params=None, intern=None, coltype=None, lset=None, smap=None,
                      vmap=None):
     """Lower `expr` to (ops, iargs, fargs, names) for the C-ABI.
@@ -994,51 +1205,7 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
         return resolve_column(e, header, columns) if header is not None and e in header else None
 
     def static_type(e):
-        """capf type of e when known without evaluating it, else None."""
-        c = column_of(e)
-        if c is not None:
-            return coltype(c) if coltype is not None else CT_TO_CAPF.get(getattr(e, "ctype", "ANY"))
-        if isinstance(e, (IntegerLit, FloatLit, StringLit, BoolLit)):
-            return _value_type(e.v)
-        if isinstance(e, NullLit):
-            return T_NULL
-        if isinstance(e, Param):
-            return _value_type((params or {}).get(e.pname))
-        if isinstance(e, (Var, ElementProperty)):  # no column: a NULL literal
-            return T_NULL
-        if isinstance(e, (ToFloat,)) or type(e).__name__ in _FLOAT_FUNCS or isinstance(e, (E_, Pi_, Rand_)):
-            return T_FLOAT
-        if type(e).__name__ in ("Labels", "Keys") and isinstance(e.expr, NullLit):
-            return T_NULL
-        if isinstance(e, (ToInteger, Size, Id)):
-            return T_INT
-        if isinstance(e, ToBoolean) or type(e).__name__ == "RegexMatch" or type(e).__name__ in _STR_MATCH:
-            return T_BOOL
-        if type(e).__name__ in _STR_FUNCS or isinstance(e, (Substring, Replace, ToString)):
-            return T_STRING
-        name = type(e).__name__
-        if name in ("Add", "Subtract", "Multiply", "Divide", "Modulo"):
-            ta, tb = static_type(e.lhs), static_type(e.rhs)
-            if name == "Add" and T_STRING in (ta, tb):
-                return T_STRING
-            if ta in (T_INT, T_FLOAT) and tb in (T_INT, T_FLOAT):
-                return T_FLOAT if T_FLOAT in (ta, tb) else T_INT
-            return None
-        if name in ("Negate", "Abs", "Ceil", "Floor", "Sign"):
-            t = static_type(e.expr)
-            return t if t in (T_INT, T_FLOAT) else None
-        if name in _CMP_NAMES or isinstance(e, (Ands, Ors, In)) or name in ("Not", "IsNull", "IsNotNull", "Exists"):
-            return T_BOOL
-        if isinstance(e, (Coalesce, CaseExpr)):  # the branches' common type (INTEGER and FLOAT: FLOAT)
-            parts = list(e.exprs) if isinstance(e, Coalesce) else \
-                [v for _, v in e.alternatives] + ([e.default] if e.default is not None else [])
-            ts = {static_type(x) for x in parts} - {T_NULL}
-            if None in ts or not ts:
-                return None if None in ts else T_NULL
-            if ts == {T_INT, T_FLOAT}:
-                return T_FLOAT
-            return ts.pop() if len(ts) == 1 else None
-        return None
+        return _static_type(e, header, columns, params, coltype)
 
     def literal_value(x):
         """(True, value) of a literal / parameter operand — string concatenations
@@ -1182,6 +1349,10 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
             emit(OP_LIT_NULL, CT_TO_CAPF.get(e.ctype, T_NULL))
         elif isinstance(e, Param):
             lit(params[e.pname])
+        elif cls in ("Head", "Last"):  # xs[0] / xs[-1] (SparkSQLExprMapper.scala:167-168)
+            container_index(ContainerIndex(e.expr, IntegerLit(0 if cls == "Head" else -1)))
+        elif cls == "Add" and static_type(e) == T_LIST:
+            not_impl(e)  # list concatenation: a table operation (table.py `_hoist_lists`)
         elif cls == "Add" and T_STRING in (static_type(e.lhs), static_type(e.rhs)):
             # string concatenation (:120-128): concat with the other side cast to
             # STRING; on the GPU one side must be a literal (a code map of the other)
@@ -1409,7 +1580,18 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
                 emit(OP_LIT_NULL, T_BOOL)  # x IN null: the rhs type is not a list (:117)
                 return
             if vals is None:
-                not_impl(e)
+                # a LIST column: a per-row scan of its elements (CAPF_OP_IN_LIST)
+                c = column_of(e.rhs)
+                t = static_type(e.rhs) if c is not None else None
+                if t == T_NULL:
+                    emit(OP_LIT_NULL, T_BOOL)  # a NULL list
+                    return
+                if t != T_LIST or coltype is None:
+                    not_impl(e)
+                et = coltype(("elem", c))
+                go(e.lhs)
+                emit(OP_IN_LIST, name_of(c), float(et))
+                return
             if not vals:
                 emit(OP_LIT_BOOL, 0)  # CTList(CTVoid) → FALSE (:115)
                 return
@@ -1635,6 +1817,7 @@ def _expr_getstate(self):
     d = dict(self.__dict__)
     d.pop("_hc", None)
     d.pop("_mk", None)
+    d.pop("_lf", None)
     return d
 
 

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from .expr import (AGG_COUNT_STAR, CAPF_TO_CT, T_BOOL, T_FLOAT, T_INT, T_LIST, T_NULL, T_STRING, Aggregator,
-                   Explode, Var, compile_program, explode_values, percentile_value)
+                   Explode, Var, compile_program, explode_values, may_hold_list_fn, percentile_value)
 
 JOIN_TYPES = {"inner": 0, "left_outer": 1, "right_outer": 2, "full_outer": 3, "cross": 4}
 
@@ -507,6 +507,10 @@ class GpuTable:
         return self._new("capf_table_select", self._h, enc[0], enc[1], enc[2], cols=enc[3])
 
     def filter(self, expr, header=None, params=None):
+        if may_hold_list_fn(expr):  # WHERE x IN xs[1..]: the list projected first, the temporaries dropped after
+            t, (expr2,), h2, tmps = self._hoist_lists([expr], header, params)
+            if tmps:
+                return t.filter(expr2, header=h2, params=params).select(*self.physicalColumns)
         prog = _program(expr, header, self, params)
         e, keep = _lib._keepalive_expr(prog)
         return self._new("capf_table_filter", self._h, byref(e), cols=self._cols)
@@ -720,7 +724,75 @@ class GpuTable:
                   int(keep.sum()), byref(mid))
         return "\x01vmap:%d" % mid.value
 
+    def _hoist_lists(self, exprs, header, params):
+        """(table, exprs', header', temporaries): every list-valued
+        sub-expression of `exprs` (expr.list_valued — Reverse, Range, a slice,
+        a concatenating Add — and a list literal of non-literal items below the
+        top of an expression; callers ask expr.may_hold_list_fn first)
+        projected to a temporary LIST column of this table, innermost first,
+        and replaced by a Var of that column (replace_exprs).  Literal
+        arguments become columns through withColumns; capf_table_list_fn builds
+        the list.  Without such a sub-expression nothing changes."""
+        from .expr import ListLit, list_fn_args, list_valued, list_values, replace_exprs, sub_exprs
+        t, h, m, tmps = self, header, {}, []
+        cols = set(self.physicalColumns)
+
+        def hoistable(e, top):
+            if isinstance(e, ListLit):
+                return not top and list_values(e, params) is None
+            return list_valued(e, header, cols, params, self._coltype)
+
+        def visit(e, top, found):
+            for x in sub_exprs(e):
+                visit(x, False, found)
+            if hoistable(e, top) and e not in found:
+                found.append(e)
+
+        found = []
+        for e in exprs:
+            visit(e, True, found)
+        if not found:
+            return self, list(exprs), header, []
+
+        def tmp():
+            tmps.append(f"\x03lf{len(tmps)}")
+            return tmps[-1]
+
+        for e in found:  # innermost first: the inner ones are columns already
+            e2 = replace_exprs(e, m)
+            c = tmp()
+            if isinstance(e2, ListLit):
+                t = t.withColumns((e2, c), header=h, params=params)
+            else:
+                fn, args = list_fn_args(e2)
+                names = []
+                for a in args:
+                    ac = None if a is None else h.get(a) if h is not None else None
+                    if a is None:
+                        names.append("")
+                    elif ac is not None and ac in t.physicalColumns:
+                        names.append(ac)
+                    else:  # a literal, a parameter or a scalar expression: a column of its own
+                        names.append(tmp())
+                        t = t.withColumns((a, names[-1]), header=h, params=params)
+                t = t._new("capf_table_list_fn", t._h, int(fn), len(names), _lib.strs(names), c.encode())
+            v = Var(c, "LIST")
+            m[e] = v
+            if h is None:
+                from .header import RecordHeader
+                h = RecordHeader({})
+            h = h.with_expr(v, c) if hasattr(h, "with_expr") else {**h, v: c}
+        return t, [replace_exprs(e, m) for e in exprs], h, tmps
+
     def withColumns(self, *columns, header=None, params=None):
+        for e, _ in columns:
+            if may_hold_list_fn(e):  # list functions: built as temporary LIST columns, dropped afterwards
+                t, exprs, h2, tmps = self._hoist_lists([e for e, _ in columns], header, params)
+                if tmps:
+                    out = t.withColumns(*zip(exprs, [c for _, c in columns]), header=h2, params=params)
+                    gone = set(tmps)
+                    return out.select(*[c for c in out.physicalColumns if c not in gone])
+                break
         lit = [(e, c) for e, c in columns if _list_items(e, params) is not None]
         if lit:  # [x, y, ...] / $list: LIST columns of per-row elements (capf_table_list_columns)
             plain = [(e, c) for e, c in columns if (e, c) not in lit]

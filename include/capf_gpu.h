@@ -241,7 +241,17 @@ enum {
    * pattern matches every subject.  A literal pattern is answered from a
    * device table per dictionary string when that examines no more strings
    * than the input has rows, else row by row.                               */
-  CAPF_OP_STR_MATCH = 96
+  CAPF_OP_STR_MATCH = 96,
+  /* x IN xs, xs a LIST column (okapi In; Morpheus array_contains,
+   * SparkSQLExprMapper.scala:161-164; expectations NullTests.scala:127-132):
+   * pops x; pushes the three-valued answer from a scan of the row's elements
+   * in LIST column names[iarg] (farg = the element's capf type, as for
+   * CAPF_OP_LIST_INDEX).  In this order: a NULL list gives NULL; an empty
+   * list FALSE (for a NULL x too); a NULL x NULL; a non-NULL element equal
+   * to x (CAPF_OP_EQ's equality, INTEGER and FLOAT numerically) TRUE;
+   * otherwise NULL when the list holds a NULL element, else FALSE.  An element
+   * type that cannot equal x's type gives NULL.                              */
+  CAPF_OP_IN_LIST = 97
 };
 
 typedef struct capf_expr {
@@ -733,6 +743,36 @@ capf_status capf_table_add_list_nulls(capf_table *t, const char *name, int32_t e
  * Nested lists are NotImplemented.  n = 0: the empty list.                  */
 capf_status capf_table_list_columns(capf_table *t, int32_t n, const char *const *cols, const char *name,
                                     capf_table **out);
+/* List functions (okapi Expr.scala:640-653 Head / Last / Reverse, :859-880
+ * Range, :1166-1176 ListSliceFromTo / ListSliceFrom / ListSliceTo, Add on
+ * lists; Flink's mapper lowers none of them — the semantics are the Morpheus
+ * lowering, SparkSQLExprMapper.scala:171-182, 265, 269, 336-338 and
+ * MorpheusFunctions.scala:79-83, with Cypher's answers for negative and
+ * crossing slice bounds; expectations FunctionTests.scala:1502-1556,
+ * 1631-1718, ExpressionTests.scala:47-80, NullTests.scala:55-63, 107).
+ * This table plus LIST column `name` = fn(args); args are column names of t,
+ * an empty name an absent slice bound / step:
+ *   SLICE   (list, from, to): Python's xs[from:to] — negative bounds count
+ *           from the end, bounds are clamped, from >= to is the empty list;
+ *           an EMPTY list gives NULL (ExpressionTests.scala:70-79), so does a
+ *           NULL list or a NULL bound.  Bounds are INTEGER.
+ *   REVERSE (list): the elements in reverse order, NULL elements included.
+ *   CONCAT  (a, b): each a LIST or a scalar column; a scalar side is a
+ *           one-element list (a NULL value a NULL element), a NULL list side
+ *           gives NULL.  Element types are equal, or INTEGER with FLOAT
+ *           (widened to FLOAT); a NULL-typed side takes the other's type;
+ *           other mixes are NotImplemented ("Lists of different inner types
+ *           are not supported", SparkSQLExprMapper.scala:179).
+ *   RANGE   (from, to, step): INTEGER columns, step 1 when absent, the end
+ *           inclusive; a direction that never arrives is the empty list, a
+ *           NULL argument a NULL list.  A step of 0, or a row of more than
+ *           2^31 - 1 elements (Spark's sequence limit), is IllegalArgument,
+ *           raised when the table is evaluated.  No length or element wraps.
+ * The node is lazy; its element type is known when it is built.
+ * A NULL-typed list argument of SLICE / REVERSE gives a NULL-typed column. */
+enum { CAPF_LIST_FN_SLICE = 0, CAPF_LIST_FN_REVERSE = 1, CAPF_LIST_FN_CONCAT = 2, CAPF_LIST_FN_RANGE = 3 };
+capf_status capf_table_list_fn(capf_table *t, int32_t fn, int32_t nargs, const char *const *args,
+                               const char *name, capf_table **out);
 /* labels(n) / keys(n) (FlinkSQLExprMapper.scala:136-153; the GetLabels /
  * GetKeys UDFs, :310-329): appends LIST<STRING> column `name` holding, per row,
  * codes[j] for each column cols[j] that holds TRUE (kinds[j] = 0, a label flag)

@@ -576,6 +576,13 @@ JNI(jlong, tableListColumns)(JNIEnv *env, jobject, jlong t, jobjectArray cols, j
   capf_table *out = nullptr;
   return fail(env, capf_table_list_columns(T(t), c.n(), c.data(), nm.p, &out)) ? 0 : H(out);
 }
+// slice / reverse / concat / range over columns (okapi Expr.scala:640-653, 859-880, 1166-1176); "" = absent
+JNI(jlong, tableListFn)(JNIEnv *env, jobject, jlong t, jint fn, jobjectArray args, jstring name) {
+  JStrs a(env, args);
+  JStr nm(env, name);
+  capf_table *out = nullptr;
+  return fail(env, capf_table_list_fn(T(t), (int32_t)fn, a.n(), a.data(), nm.p, &out)) ? 0 : H(out);
+}
 JNI(jlong, tableWithColumns)(JNIEnv *env, jobject, jlong t, jobjectArray exprs,
                              jobjectArray names) {  // Table.scala:170
   Programs e(env, exprs);

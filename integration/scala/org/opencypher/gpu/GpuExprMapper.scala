@@ -199,6 +199,16 @@ object GpuExprMapper {
       }
     }
 
+    // head / last of a LIST column: CAPF_OP_LIST_INDEX with the index 0 / -1 (an
+    // empty or NULL list gives NULL); of NULL, NULL
+    def headLast(xs: Expr, index: Long): Unit = xs match {
+      case NullLit(_) => emit(LitNull, Native.TypeNull)
+      case _ if xs.cypherType.material.isInstanceOf[CTList] && physical(xs).isDefined =>
+        val elem = GpuTypes.fromCypher(xs.cypherType.material.asInstanceOf[CTList].inner)
+        emit(LitInt, index); emit(ListIndex, nameIndex(physical(xs).get), elem.toDouble)
+      case _ => throw NotImplementedException(s"GPU head / last of $xs")
+    }
+
     def go(e: Expr): Unit = e match {
       case _: Var | _: HasLabel | _: HasType | _: StartNode | _: EndNode | _: ElementProperty =>
         physical(e) match {
@@ -266,6 +276,15 @@ object GpuExprMapper {
       // index in the id's top byte, as graph.py ScanGraph.union_all does
       case PrefixId(x, prefix) => go(x); emit(LitInt, (prefix.toLong & 0xFFL) << 56); emit(Add_)
       case Exists(x) => go(x); emit(IsNotNull_)                            // :90
+      // head(xs) / last(xs) = xs[0] / xs[-1] (SparkSQLExprMapper.scala:167-168) on a LIST column
+      case h: Head => headLast(h.expr, 0L)
+      case l: Last => headLast(l.expr, -1L)
+      // x IN a LIST column (array_contains, SparkSQLExprMapper.scala:161-164): a per-row scan,
+      // three-valued as NullTests.scala:127-132; literal and parameter lists keep the lowering below
+      case in: In if listValues(in.rhs).isEmpty && in.rhs.cypherType.material.isInstanceOf[CTList] &&
+        physical(in.rhs).isDefined =>
+        val elem = GpuTypes.fromCypher(in.rhs.cypherType.material.asInstanceOf[CTList].inner)
+        go(in.lhs); emit(Native.OpInList, nameIndex(physical(in.rhs).get), elem.toDouble)
       case In(lhs, rhs) =>                                                 // :114-118
         val vals = listValues(rhs).getOrElse(throw NotImplementedException(s"GPU IN over $rhs"))
         if (vals.isEmpty) emit(LitBool, 0L)                                // CTList(CTVoid) → FALSE

@@ -61,8 +61,11 @@ final class GpuTable private (private[gpu] val handle: Long)(implicit val sessio
     wrap(Native.tableSelect(handle, all.map(_._1).toArray, all.map(_._2).toArray))
   }
 
-  override def filter(expr: Expr)(implicit header: RecordHeader, parameters: CypherMap): GpuTable = // :81
+  override def filter(expr: Expr)(implicit header: RecordHeader, parameters: CypherMap): GpuTable = { // :81
+    val (t, Seq(e2), h2, tmps) = hoistLists(Seq(expr), header, parameters)
+    if (tmps.nonEmpty) return t.filter(e2)(h2, parameters).select(physicalColumns: _*)
     wrap(Native.tableFilter(handle, GpuExprMapper.program(expr, header, this, parameters)))
+  }
 
   override def drop(cols: String*): GpuTable = wrap(Native.tableDrop(handle, cols.toArray))   // :89
 
@@ -98,7 +101,73 @@ final class GpuTable private (private[gpu] val handle: Long)(implicit val sessio
       lowered.map(_._3).toArray, lowered.map(_._4).toArray, aggs.map(_._1).toArray))
   }
 
+  /** The list-valued function expressions built by capf_table_list_fn (table.py
+    * `_hoist_lists`): reverse, range, the three slices and an Add with a list side
+    * (SparkSQLExprMapper.scala:171-182, 265, 269, 336-338), as (selector, arguments). */
+  private def listFnArgs(e: Expr): Option[(Int, Seq[Option[Expr]])] = e match {
+    case r: Reverse if r.expr.cypherType.material.isInstanceOf[CTList] || r.expr.cypherType.material == CTNull =>
+      Some(Native.ListFnReverse -> Seq(Some(r.expr)))
+    case r: Range => Some(Native.ListFnRange -> Seq(Some(r.from), Some(r.to), r.o))
+    case s: ListSliceFromTo => Some(Native.ListFnSlice -> Seq(Some(s.list), Some(s.from), Some(s.to)))
+    case s: ListSliceFrom => Some(Native.ListFnSlice -> Seq(Some(s.list), Some(s.from), None))
+    case s: ListSliceTo => Some(Native.ListFnSlice -> Seq(Some(s.list), None, Some(s.to)))
+    case a: Add if a.lhs.cypherType.material.isInstanceOf[CTList] || a.rhs.cypherType.material.isInstanceOf[CTList] =>
+      Some(Native.ListFnConcat -> Seq(Some(a.lhs), Some(a.rhs)))
+    case _ => None
+  }
+
+  /** Every list-valued sub-expression (listFnArgs; a list literal of per-row items below
+    * the top) projected to a temporary LIST column, innermost first, and replaced by a
+    * Var of that column: (table, rewritten expressions, header, temporaries). */
+  private def hoistLists(exprs: Seq[Expr], header: RecordHeader, parameters: CypherMap)
+  : (GpuTable, Seq[Expr], RecordHeader, Seq[String]) = {
+    var t = this
+    var h = header
+    var tmps = Vector.empty[String]
+    var done = Map.empty[Expr, Expr]
+    def tmp(): String = { tmps :+= s"\u0003lf${tmps.size}"; tmps.last }
+    def perRowLiteral(e: Expr): Boolean = e match {
+      case ListLit(items) => items.exists(i => !i.isInstanceOf[Lit[_]] && !i.isInstanceOf[Param])
+      case _ => false
+    }
+    def lower(e: Expr, top: Boolean): Expr = done.getOrElse(e, {
+      val kids = e.children.map(c => lower(c, top = false))
+      val e2 = if (kids.isEmpty || e.isInstanceOf[ListLit]) e else e.withNewChildren(kids.toArray)
+      val col: Option[String] = listFnArgs(e2) match {
+        case Some((fn, args)) =>
+          val names = args.map {
+            case None => ""
+            case Some(a) if h.contains(a) && t.physicalColumns.contains(h.column(a)) => h.column(a)
+            case Some(a) => val c = tmp(); t = t.withColumns(a -> c)(h, parameters); c
+          }
+          val c = tmp()
+          t = wrap(Native.tableListFn(t.handle, fn, names.toArray, c))
+          Some(c)
+        case None if !top && perRowLiteral(e2) =>
+          val c = tmp(); t = t.withColumns(e2 -> c)(h, parameters); Some(c)
+        case None => None
+      }
+      col match {
+        case Some(c) =>
+          val v = Var(c)(e2.cypherType)
+          h = h.withExpr(v)
+          // the temporary is read under its own name
+          if (h.column(v) != c) t = t.select(t.physicalColumns.map(x => if (x == c) c -> h.column(v) else x -> x): _*)
+          done += e -> v
+          v
+        case None => e2
+      }
+    })
+    val out = exprs.map(lower(_, top = true))
+    (t, out, h, tmps.map(c => if (h.contains(Var(c)())) h.column(Var(c)()) else c))
+  }
+
   override def withColumns(columns: (Expr, String)*)(implicit header: RecordHeader, parameters: CypherMap): GpuTable = { // :170
+    val (hoisted, exprs, h2, tmps) = hoistLists(columns.map(_._1), header, parameters)
+    if (tmps.nonEmpty) {  // list functions: temporary LIST columns, dropped afterwards
+      val out = hoisted.withColumns(exprs.zip(columns.map(_._2)): _*)(h2, parameters)
+      return out.select(out.physicalColumns.filterNot(tmps.contains): _*)
+    }
     val (literalLists, others) = columns.partition { case (e, _) => listItems(e, parameters).isDefined }
     if (literalLists.nonEmpty) {  // [x, y, ...] / $list (FlinkSQLExprMapper.scala:71, 75): capf_table_list_columns
       val base = if (others.isEmpty) this else withColumns(others: _*)

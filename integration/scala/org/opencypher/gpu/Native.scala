@@ -60,6 +60,13 @@ object Native {
 
   // CAPF_OP_STR_MATCH (opcode 96) and its kinds (the instruction's iarg)
   final val OpStrMatch = 96
+  // CAPF_OP_IN_LIST (opcode 97): x IN a LIST column; farg = the element type
+  final val OpInList = 97
+  // CAPF_LIST_FN_* selectors of capf_table_list_fn
+  final val ListFnSlice = 0
+  final val ListFnReverse = 1
+  final val ListFnConcat = 2
+  final val ListFnRange = 3
   final val StrMatchStartsWith = 0
   final val StrMatchEndsWith = 1
   final val StrMatchContains = 2
@@ -171,6 +178,8 @@ object Native {
                                 elemValid: java.nio.ByteBuffer): Long
   @native def tableNameList(table: Long, cols: Array[String], kinds: Array[Int], codes: Array[Long], name: String): Long
   @native def tableListColumns(table: Long, cols: Array[String], name: String): Long
+  // capf_table_list_fn: fn = ListFn*, args = column names ("" = an absent slice bound / step)
+  @native def tableListFn(table: Long, fn: Int, args: Array[String], name: String): Long
   @native def tableShow(table: Long, rows: Int): Unit
 
   // graph inputs (EdgeListDataSource.scala:56-92; synthetic R-MAT / node ranges)
