@@ -589,31 +589,37 @@ __global__ void k_count_ids(ColView ids, int64_t n, int64_t lo, int64_t hi, uint
 // (ColRef, Leaf, JoinGraph: join_graph.h)
 static bool program_is_uniqueness(const Program &p, std::vector<std::pair<int, int>> &pairs) {
   // [COL a, COL b, EQ, NOT] | [COL a, COL b, NEQ], possibly combined by AND(k)
+  // — one AND over all terms, or the chunked form of a long conjunction (AND
+  // over the terms so far, its result the first operand of the next AND): any
+  // grouping that leaves one value is the conjunction of all terms
   const auto &c = p.code;
   size_t i = 0;
-  int terms = 0;
+  int terms = 0, depth = 0;
   while (i < c.size()) {
     if (i + 2 < c.size() && c[i].op == OP_COL && c[i + 1].op == OP_COL) {
       if (c[i + 2].op == OP_NEQ) {
         pairs.emplace_back((int)c[i].i, (int)c[i + 1].i);
         i += 3;
         ++terms;
+        ++depth;
         continue;
       }
       if (i + 3 < c.size() && c[i + 2].op == OP_EQ && c[i + 3].op == OP_NOT) {
         pairs.emplace_back((int)c[i].i, (int)c[i + 1].i);
         i += 4;
         ++terms;
+        ++depth;
         continue;
       }
     }
-    if (c[i].op == OP_AND && i + 1 == c.size() && c[i].i == terms) {
+    if (c[i].op == OP_AND && c[i].i >= 1 && c[i].i <= depth) {
+      depth -= (int)c[i].i - 1;
       ++i;
       continue;
     }
     return false;
   }
-  return terms > 0;
+  return terms > 0 && depth == 1;
 }
 
 bool collect(const NodePtr &n, JoinGraph &g, std::vector<ColRef> &out) {

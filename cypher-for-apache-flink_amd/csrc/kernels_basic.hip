@@ -888,11 +888,16 @@ __device__ inline Val load_col(const ColView &c, int64_t r) {
   return mk(ld_int(c, r), c.type, 0);
 }
 
-// -1 less, 0 equal, 1 greater (non-null operands)
+// -1 less, 0 equal, 1 greater, CMP_UNORDERED when a NaN is involved (non-null
+// operands).  Java primitive (IEEE) comparison, what Flink's generated code
+// does on double: an unordered pair is neither equal, less nor greater — only
+// <> holds.  (The total order of sort / group / distinct / min / max, NaN last
+// and equal to itself, lives in their own key code, not here.)
+constexpr int CMP_UNORDERED = 2;
 __device__ inline int cmp_vals(const Val &a, const Val &b) {
   if (a.t == CAPF_TYPE_FLOAT64 || b.t == CAPF_TYPE_FLOAT64) {
     double x = vf(a), y = vf(b);
-    return x < y ? -1 : (x > y ? 1 : 0);
+    return x < y ? -1 : (x > y ? 1 : (x == y ? 0 : CMP_UNORDERED));
   }
   return a.b < b.b ? -1 : (a.b > b.b ? 1 : 0);
 }
@@ -970,8 +975,8 @@ __device__ Val run_program(const Instr *code, int ncode, const ColView *cols, in
           case OP_NEQ: res = c != 0; break;
           case OP_LT: res = c < 0; break;
           case OP_LE: res = c <= 0; break;
-          case OP_GT: res = c > 0; break;
-          default: res = c >= 0; break;
+          case OP_GT: res = c == 1; break;
+          default: res = c == 0 || c == 1; break;
         }
         st[sp++] = mkb(res);
         break;

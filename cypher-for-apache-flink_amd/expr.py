@@ -40,6 +40,7 @@ OP_ROUND, OP_ABS, OP_CEIL, OP_FLOOR, OP_SIGN, OP_SQRT, OP_LOG, OP_LOG10, OP_EXP 
 OP_SIN, OP_COS, OP_TAN, OP_ASIN, OP_ACOS, OP_ATAN, OP_DEGREES, OP_RADIANS = 79, 80, 81, 82, 83, 84, 85, 86
 OP_ATAN2, OP_TO_BOOLEAN, OP_IN_SET, OP_STR_MAP, OP_VALUE_MAP = 87, 88, 89, 90, 91
 OP_STR_TO_NUM, OP_RAND, OP_LIST_INDEX, OP_STR_RANK, OP_STR_MATCH, OP_IN_LIST = 92, 93, 94, 95, 96, 97
+NARY_CHUNK = 8   # operands AND / OR / COALESCE take per instruction (longer ones fold in chunks)
 IN_SET_MIN = 17  # list length from which IN runs as a session-set lookup (shorter: an OR of equalities)
 
 # aggregators
@@ -1129,13 +1130,14 @@ def _static_type(e, header, columns, params=None, coltype=None):
             return coltype(("elem", cx)) if coltype(cx) == T_LIST else T_NULL if coltype(cx) == T_NULL else None
         return T_NULL if isinstance(x, NullLit) else None
     name = type(e).__name__
-    if name == "Add":  # a list side: concatenation
-        for x in (e.lhs, e.rhs):
-            if isinstance(x, ListLit) or (isinstance(x, Param) and isinstance((params or {}).get(x.pname), (list, tuple))) \
-                    or _static_type(x, header, columns, params, coltype) == T_LIST:
-                return T_LIST
     if name in ("Add", "Subtract", "Multiply", "Divide", "Modulo"):
+        # (each side typed once: typing a side twice doubles the work per level of a long sum)
         ta, tb = _static_type(e.lhs, header, columns, params, coltype), _static_type(e.rhs, header, columns, params, coltype)
+        if name == "Add":  # a list side: concatenation
+            for x, t in ((e.lhs, ta), (e.rhs, tb)):
+                if isinstance(x, ListLit) or t == T_LIST or \
+                        (isinstance(x, Param) and isinstance((params or {}).get(x.pname), (list, tuple))):
+                    return T_LIST
         if name == "Add" and T_STRING in (ta, tb):
             return T_STRING
         if ta in (T_INT, T_FLOAT) and tb in (T_INT, T_FLOAT):
@@ -1322,6 +1324,22 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
         et = coltype(("elem", c))
         go(e.index)
         emit(OP_LIST_INDEX, name_of(c), float(et))
+
+    def nary(op, xs):
+        """AND / OR / COALESCE of any arity: at most NARY_CHUNK operands on the
+        stack, then the op, its result the first operand of the next chunk —
+        3-valued AND and OR are associative, and so is COALESCE (a Val carries
+        its own type).  The interpreter's stack is 24 deep whatever the arity
+        (okapi flattens a long WHERE into one Ands); up to NARY_CHUNK operands
+        the program is the single n-ary op the filter fast path reads."""
+        k = 0
+        for x in xs:
+            if k == NARY_CHUNK:
+                emit(op, k)
+                k = 1
+            go(x)
+            k += 1
+        emit(op, k)
 
     def go(e):
         cls = type(e).__name__
@@ -1518,20 +1536,14 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
             if not e.exprs:
                 emit(OP_LIT_BOOL, 1)
                 return
-            for x in e.exprs:
-                go(x)
-            emit(OP_AND, len(e.exprs))
+            nary(OP_AND, e.exprs)
         elif isinstance(e, Ors):
             if not e.exprs:
                 emit(OP_LIT_BOOL, 0)
                 return
-            for x in e.exprs:
-                go(x)
-            emit(OP_OR, len(e.exprs))
+            nary(OP_OR, e.exprs)
         elif isinstance(e, Coalesce):
-            for x in e.exprs:
-                go(x)
-            emit(OP_COALESCE, len(e.exprs))
+            nary(OP_COALESCE, e.exprs)
         elif cls == "Id":
             go(e.expr)  # the id column (FlinkSQLExprMapper.scala:134)
         elif cls in ("StartNodeFunction", "EndNodeFunction"):

@@ -209,6 +209,16 @@ object GpuExprMapper {
       case _ => throw NotImplementedException(s"GPU head / last of $xs")
     }
 
+    // AND / OR / COALESCE of any arity: at most 8 operands on the stack, then the
+    // op, its result the first operand of the next chunk (3-valued AND and OR are
+    // associative, so is COALESCE) — the interpreter's stack is 24 deep and
+    // okapi flattens a long WHERE into one Ands (expr.py's `nary`)
+    def nary(xs: Seq[Expr], op: Int): Unit = {
+      var k = 0
+      xs.foreach { x => if (k == 8) { emit(op, 8L); k = 1 }; go(x); k += 1 }
+      emit(op, k.toLong)
+    }
+
     def go(e: Expr): Unit = e match {
       case _: Var | _: HasLabel | _: HasType | _: StartNode | _: EndNode | _: ElementProperty =>
         physical(e) match {
@@ -231,9 +241,9 @@ object GpuExprMapper {
       case GreaterThanOrEqual(l, r) => ordered(l, r, Ge)
       case Not(x) => go(x); emit(Not_)
       case Ands(xs) if xs.isEmpty => emit(LitBool, 1L)
-      case Ands(xs) => xs.foreach(go); emit(And, xs.size.toLong)
+      case Ands(xs) => nary(xs.toSeq, And)
       case Ors(xs) if xs.isEmpty => emit(LitBool, 0L)
-      case Ors(xs) => xs.foreach(go); emit(Or, xs.size.toLong)
+      case Ors(xs) => nary(xs.toSeq, Or)
       case IsNull(x) => go(x); emit(IsNull_)
       case IsNotNull(x) => go(x); emit(IsNotNull_)
       case Add(l, r) => go(l); go(r); emit(Add_)
@@ -269,7 +279,7 @@ object GpuExprMapper {
         // (Flink's ARRAY `at` is 1-based); farg = the element type
         val elem = GpuTypes.fromCypher(c.cypherType.material.asInstanceOf[CTList].inner)
         go(i); emit(ListIndex, nameIndex(physical(c).get), elem.toDouble)
-      case Coalesce(xs) => xs.foreach(go); emit(Coalesce_, xs.size.toLong)
+      case Coalesce(xs) => nary(xs.toSeq, Coalesce_)
       case Id(x) => go(x)                                                  // FlinkSQLExprMapper.scala:134
       case ToId(x) => go(x)                                                // ids are LONGs (FlinkConversions.scala:47-53)
       // graph.unionAll's member tag (RelationalPlanner.scala:429-432): the graph

@@ -200,8 +200,16 @@ def _arith(a, b, op):
             zero = y == 0
             ok = ok & ~zero
             ys = np.where(zero, 1, y)
-            # Java long division truncates toward zero
-            q = np.abs(x) // np.abs(ys) * np.sign(x) * np.sign(ys)
+            # Java long division truncates toward zero: the floored quotient,
+            # one up where the signs differ and the division is inexact.  (No
+            # |x|: abs(Long.MIN_VALUE) overflows.)  MIN / -1 wraps to MIN and
+            # MIN % -1 is 0 (JLS 15.17.2-3), set apart so that numpy never
+            # divides that pair.
+            m1 = ys == -1
+            yd = np.where(m1, 1, ys)
+            q = x // yd
+            q = q + ((x - q * yd != 0) & ((x < 0) != (yd < 0)))
+            q = np.where(m1, -x, q)
             r = q if op == "div" else x - q * ys
     return Val(T_INT, r, ok)
 
@@ -275,6 +283,7 @@ def evaluate(e, table, header, params):
                 out = np.array([_jstr(u, a.t) + _jstr(v, b.t) if oa and ob else None
                                 for u, v, oa, ob in zip(a.v, b.v, a.ok, b.ok)], dtype=object)
                 return Val(T_STRING, out, a.ok & b.ok)
+            return _arith(a, b, "add")  # (the sides evaluated once: twice doubles the work per level of a sum)
         ar_ops = {"Add": "add", "Subtract": "sub", "Multiply": "mul", "Divide": "div", "Modulo": "mod"}
         if name in ar_ops:
             return _arith(go(x.lhs), go(x.rhs), ar_ops[name])
