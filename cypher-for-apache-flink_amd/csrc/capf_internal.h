@@ -177,7 +177,7 @@ enum Op : int32_t {
   OP_TO_BOOLEAN = CAPF_OP_TO_BOOLEAN, OP_IN_SET = CAPF_OP_IN_SET, OP_STR_MAP = CAPF_OP_STR_MAP,
   OP_VALUE_MAP = CAPF_OP_VALUE_MAP, OP_STR_TO_NUM = CAPF_OP_STR_TO_NUM, OP_RAND = CAPF_OP_RAND,
   OP_LIST_INDEX = CAPF_OP_LIST_INDEX, OP_STR_RANK = CAPF_OP_STR_RANK,
-  OP_STR_MATCH = CAPF_OP_STR_MATCH, OP_IN_LIST = CAPF_OP_IN_LIST
+  OP_STR_MATCH = CAPF_OP_STR_MATCH, OP_IN_LIST = CAPF_OP_IN_LIST, OP_LAMBDA = CAPF_OP_LAMBDA
 };
 // a program name that refers to a session literal set ("\x01set:<id>"), not a column
 inline bool is_literal_set_name(const std::string &nm) { return nm.size() > 5 && nm.compare(0, 5, "\x01set:") == 0; }
@@ -273,7 +273,7 @@ __device__ inline bool ft_load(const FtOperand &o, int64_t r, int64_t &val) {
 // ------------------------------------------------------------- plan nodes
 enum class Kind {
   Source, Select, Filter, Join, Union, Distinct, Group, WithColumns, OrderBy, Skip, Limit, Explode, NameList,
-  ListColumns, ListFn
+  ListColumns, ListFn, ListLambda
 };
 
 struct AggSpec {
@@ -324,6 +324,11 @@ struct Node {
   // ListFn (capf_table_list_fn): list_fn over the child's columns name_cols
   // (-1: an absent slice bound / step), element type list_elem
   int32_t list_fn = 0;
+  // ListLambda (capf_table_list_lambda): kind list_fn over LIST column
+  // name_cols[0] (REDUCE: name_cols[1] = init); exprs[0] = pred, exprs[1] =
+  // body (empty code: absent); list_elem = the element / result type, and
+  // lambda_types the types of the lambda slots the programs were checked with
+  std::vector<Type> lambda_types;
 
   // memoised result
   std::mutex mu;
@@ -474,8 +479,9 @@ const ColStats &column_stats(Session *s, const ColPtr &c);
 ColView view_of(const ColPtr &c);
 
 // Type inference of a program against a schema (host side).
+// (lambda: the types of the lambda slots CAPF_OP_LAMBDA may push; none outside a lambda body)
 Type infer_type(const Program &p, const std::vector<std::string> &names,
-                const std::vector<Type> &types);
+                const std::vector<Type> &types, const std::vector<Type> *lambda = nullptr);
 
 // ---- kernels (implemented in *.hip)
 // Evaluate a program over `n` rows; writes a column of type `out_type`.
@@ -582,6 +588,11 @@ ColPtr list_from_columns(Session *s, const Data &d, const std::vector<int> &cols
 // slice / reverse / concat / range (capf_table_list_fn) over columns `cols` of d
 // (-1: absent); `elem` the result's element type.
 ColPtr list_fn_column(Session *s, const Data &d, int32_t fn, const std::vector<int> &cols, Type elem);
+// a lambda expression over LIST column list_col of d (capf_table_list_lambda,
+// kernels_basic.hip): pred / body may be empty (absent); init_col < 0 but for
+// REDUCE; out = the element type (COMPREHENSION) or the result type.
+ColPtr list_lambda_column(Session *s, const Data &d, const std::vector<std::string> &names, int32_t kind,
+                          int list_col, const Program &pred, const Program &body, int init_col, Type out);
 // collect(arg) per group (lists.hip): a Type::List column of g.ngroups lists.
 ColPtr collect_lists(Session *s, const Grouping &g, int64_t nrows, const ColPtr &arg,
                      bool distinct);

@@ -10,6 +10,7 @@
 
 #include "capf_internal.h"
 #include "device_common.h"
+#include "list_search.h"
 #include "str_match.h"
 
 namespace capf {
@@ -950,7 +951,14 @@ __device__ inline Val math1(int32_t op, const Val &a) {
 constexpr int MAX_STACK = 24;
 constexpr int MAX_LDS_CODE = 96;
 
-__device__ Val run_program(const Instr *code, int ncode, const ColView *cols, int64_t r) {
+// r: the row the columns and list opcodes read; lam: the (at most two) lambda
+// slots of a per-element evaluation (k_lam_*), absent for a per-row one
+// (k_eval and every caller from before lambdas, which instantiate LAM = false:
+// their code holds no CAPF_OP_LAMBDA branch and no slot pointer, so their
+// registers and scratch stay what they were).
+template <bool LAM = false>
+__device__ Val run_program(const Instr *code, int ncode, const ColView *cols, int64_t r,
+                           const Val *lam = nullptr) {
   Val st[MAX_STACK];
   int sp = 0;
   for (int pc = 0; pc < ncode; ++pc) {
@@ -1285,7 +1293,15 @@ __device__ Val run_program(const Instr *code, int ncode, const ColView *cols, in
         }
         break;
       }
-      default: st[sp++] = mknull(CAPF_TYPE_NULL); break;
+      default:
+        if constexpr (LAM) {  // CAPF_OP_LAMBDA: lambda slot in.i
+          if (in.op == OP_LAMBDA) {
+            st[sp++] = lam[in.i & 1];
+            break;
+          }
+        }
+        st[sp++] = mknull(CAPF_TYPE_NULL);
+        break;
     }
   }
   return st[0];
@@ -1484,7 +1500,7 @@ static DeviceProgram upload_program(Session *s, const Program &p,
   for (auto &in : code) {
     switch (in.op) {
       case OP_COL: case OP_LIT_INT: case OP_LIT_FLOAT: case OP_LIT_BOOL: case OP_LIT_STRING:
-      case OP_LIT_NULL: case OP_LIST_SIZE: case OP_RAND: depth++; break;
+      case OP_LIT_NULL: case OP_LIST_SIZE: case OP_RAND: case OP_LAMBDA: depth++; break;
       case OP_AND: case OP_OR: case OP_COALESCE: depth -= (int)in.i - 1; break;
       case OP_NOT: case OP_IS_NULL: case OP_IS_NOT_NULL: case OP_NEG: case OP_TO_FLOAT:
       case OP_TO_INTEGER: case OP_STR_LEN: case OP_TO_BOOLEAN: case OP_IN_SET: case OP_STR_MAP:
@@ -1548,6 +1564,318 @@ ColPtr eval_program(Session *s, const Program &p, const std::vector<std::string>
                      (uint8_t *)nullptr);
   KERNEL_CHECK();
   return o;
+}
+
+// ------------------------------------------------------- lambda expressions
+// [x IN xs WHERE p | e], filter, any / all / none / single and reduce
+// (capf_table_list_lambda; okapi Expr.scala:199, 1178-1237; the Morpheus
+// lowering SparkSQLExprMapper.scala:340-395): the interpreter run once per list
+// ELEMENT, slot 0 bound to the element, columns and list opcodes read at the
+// row that owns it.  They live beside k_eval because run_program is one
+// non-inline device function of this translation unit.
+//   k_lam_pred: one thread per source element, tiles of 256; the tile's row
+//     window by two wave-wide searches, the element's row by bisection inside
+//     it (list_search.h, as k_lfn_fill); flag[q] = pred is TRUE and the list
+//     at the row is not NULL.
+//   one exclusive scan of the flags → pos[q], the kept total;
+//   k_lam_kept: one thread per source element, kept[pos[q]] = q;
+//   k_lam_rows: one thread per row, the new offsets pos[off[r]] or the
+//     quantifier's BOOLEAN from #T = pos[off[r + 1]] − pos[off[r]];
+//   k_lam_map: one thread per OUTPUT element, its row by the same windowed
+//     search over the result's offsets, the extract program (or a plain copy
+//     through lfn_store) stored contiguously;
+//   k_lam_reduce: one thread per row, the one sequential walk (a fold with a
+//     general body — FLOAT addition is not associative — cannot be split
+//     without changing results).
+struct LamProg {
+  const Instr *code;
+  const ColView *cols;
+  int32_t ncode, ncols;
+};
+struct LamList {
+  const int64_t *off;    // offsets [n + 1], off[0] = 0
+  const uint8_t *valid;  // list validity (may be null)
+  ColView e;             // the element column (type NULL: NULL-typed elements)
+};
+
+constexpr int LAM_BLOCK = 256;
+
+// the program and its views staged in LDS, as k_eval does
+__device__ inline void lam_stage(const LamProg &p, Instr *s_code, ColView *s_cols, const Instr *&cp,
+                                 const ColView *&cv) {
+  const bool lds_code = p.ncode <= MAX_LDS_CODE, lds_cols = p.ncols <= 32;
+  if (lds_code)
+    for (int i = threadIdx.x; i < p.ncode; i += blockDim.x) s_code[i] = p.code[i];
+  if (lds_cols)
+    for (int i = threadIdx.x; i < p.ncols; i += blockDim.x) s_cols[i] = p.cols[i];
+  __syncthreads();
+  cp = lds_code ? s_code : p.code;
+  cv = lds_cols ? s_cols : p.cols;
+}
+
+// waves 0 and 1: the rows of the first and last element of the tile at o0 into s_win
+__device__ inline void lam_window(const int64_t *off, int64_t n, int64_t o0, int64_t total, int64_t *s_win) {
+  if (threadIdx.x < 128) {
+    const int64_t last = o0 + LAM_BLOCK - 1 < total ? o0 + LAM_BLOCK - 1 : total - 1;
+    const int w = threadIdx.x >> 6;
+    const int64_t r = lfn_row_of_wave(off, n, w ? last : o0, threadIdx.x & 63);
+    if ((threadIdx.x & 63) == 0) s_win[w] = r;
+  }
+  __syncthreads();
+}
+
+// v as a value of type `type` into slot i (k_eval's store)
+__device__ inline void lam_store(const Val &v, int32_t type, void *out, uint8_t *valid, int64_t i) {
+  if (valid) valid[i] = v.nul ? 0 : 1;
+  if (type == CAPF_TYPE_BOOL) ((uint8_t *)out)[i] = (!v.nul && v.b != 0) ? 1 : 0;
+  else if (type == CAPF_TYPE_FLOAT64) ((double *)out)[i] = v.nul ? 0.0 : vf(v);
+  else ((int64_t *)out)[i] = v.nul ? 0 : v.b;
+}
+
+// total = l.off[n] > 0; flag [total]
+__global__ __launch_bounds__(LAM_BLOCK) void k_lam_pred(LamProg p, LamList l, int64_t n, int64_t total,
+                                                        int64_t *flag) {
+  __shared__ Instr s_code[MAX_LDS_CODE];
+  __shared__ ColView s_cols[32];
+  __shared__ int64_t s_win[2];
+  const Instr *cp;
+  const ColView *cv;
+  lam_stage(p, s_code, s_cols, cp, cv);
+  for (int64_t q0 = (int64_t)blockIdx.x * LAM_BLOCK; q0 < total; q0 += (int64_t)gridDim.x * LAM_BLOCK) {
+    lam_window(l.off, n, q0, total, s_win);
+    const int64_t q = q0 + threadIdx.x;
+    if (q < total) {
+      const int64_t r = lfn_row_of(l.off, s_win[0], s_win[1], q);
+      int64_t f = 0;
+      if (!(l.valid && !l.valid[r])) {  // (elements stored under a NULL list: 0)
+        const Val x = load_col(l.e, q);
+        const Val v = run_program<true>(cp, p.ncode, cv, r, &x);
+        f = (!v.nul && v.b != 0) ? 1 : 0;
+      }
+      flag[q] = f;
+    }
+    __syncthreads();  // (the window is rewritten by the next step)
+  }
+}
+
+__global__ void k_lam_kept(const int64_t *flag, const int64_t *pos, int64_t total, int64_t *kept) {
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x)
+    if (flag[q]) kept[pos[q]] = q;
+}
+
+// noff [n + 1] (a comprehension) or out / out_valid [n] (a quantifier); pos
+// [total + 1], null when the lists hold no element
+__global__ void k_lam_rows(const int64_t *off, const uint8_t *lvalid, const int64_t *pos, int64_t n, int32_t kind,
+                           int64_t *noff, uint8_t *out, uint8_t *out_valid) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= n; r += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t o0 = off[r];
+    const int64_t p0 = pos ? pos[o0] : 0;
+    if (noff) noff[r] = p0;
+    if (!out || r == n) continue;
+    const int64_t o1 = off[r + 1];
+    const int64_t c = pos ? pos[o1] - p0 : 0, len = o1 - o0;
+    const bool ok = !(lvalid && !lvalid[r]);
+    const bool b = kind == CAPF_LAMBDA_ANY ? c > 0 : kind == CAPF_LAMBDA_NONE ? c == 0
+                   : kind == CAPF_LAMBDA_ALL ? c == len : c == 1;
+    out[r] = ok && b ? 1 : 0;
+    out_valid[r] = ok ? 1 : 0;
+  }
+}
+
+// roff: the result's offsets [n + 1], roff[n] = total > 0; kept [total] the
+// source element of each output element (null: the identity); p.ncode = 0: no
+// extract, the element is copied
+__global__ __launch_bounds__(LAM_BLOCK) void k_lam_map(LamProg p, LamList l, int64_t n, const int64_t *roff,
+                                                       const int64_t *kept, int64_t total, int32_t elem,
+                                                       void *child, uint8_t *cvalid) {
+  __shared__ Instr s_code[MAX_LDS_CODE];
+  __shared__ ColView s_cols[32];
+  __shared__ int64_t s_win[2];
+  const Instr *cp;
+  const ColView *cv;
+  lam_stage(p, s_code, s_cols, cp, cv);
+  const bool copy = p.ncode == 0;
+  for (int64_t o0 = (int64_t)blockIdx.x * LAM_BLOCK; o0 < total; o0 += (int64_t)gridDim.x * LAM_BLOCK) {
+    if (!copy) lam_window(roff, n, o0, total, s_win);
+    const int64_t o = o0 + threadIdx.x;
+    if (o < total) {
+      const int64_t q = kept ? kept[o] : o;
+      if (copy) {
+        lfn_store(l.e, q, elem, child, cvalid, o);
+      } else {
+        const int64_t r = lfn_row_of(roff, s_win[0], s_win[1], o);
+        const Val x = load_col(l.e, q);
+        lam_store(run_program<true>(cp, p.ncode, cv, r, &x), elem, child, cvalid, o);
+      }
+    }
+    if (!copy) __syncthreads();  // (the window is rewritten by the next step)
+  }
+}
+
+// slot 0 the accumulator (init at row r, an INTEGER widened when the result
+// is FLOAT), slot 1 the element
+__global__ void k_lam_reduce(LamProg p, LamList l, ColView init, int64_t n, int32_t out_type, void *out,
+                             uint8_t *out_valid) {
+  __shared__ Instr s_code[MAX_LDS_CODE];
+  __shared__ ColView s_cols[32];
+  const Instr *cp;
+  const ColView *cv;
+  lam_stage(p, s_code, s_cols, cp, cv);
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
+    Val lam[2];
+    if (l.valid && !l.valid[r]) {
+      lam[0] = mknull(out_type);
+    } else {
+      lam[0] = load_col(init, r);
+      if (out_type == CAPF_TYPE_FLOAT64 && lam[0].t == CAPF_TYPE_INT64 && !lam[0].nul) lam[0] = mkf((double)lam[0].b);
+      for (int64_t q = l.off[r]; q < l.off[r + 1]; ++q) {
+        lam[1] = load_col(l.e, q);
+        lam[0] = run_program<true>(cp, p.ncode, cv, r, lam);
+      }
+    }
+    lam_store(lam[0], out_type, out, out_valid, r);
+  }
+}
+
+// Can program p give NULL?  Conservative: an opcode it does not know can.
+static bool program_nullable(const Program &p, const std::vector<std::string> &names, const Data &d,
+                             bool elem_nullable) {
+  std::vector<char> st;
+  auto pop = [&]() {
+    const char v = st.empty() ? 1 : st.back();
+    if (!st.empty()) st.pop_back();
+    return v;
+  };
+  for (auto &in : p.code) {
+    switch (in.op) {
+      case OP_LIT_INT: case OP_LIT_FLOAT: case OP_LIT_BOOL: case OP_LIT_STRING: st.push_back(0); break;
+      case OP_LAMBDA: st.push_back(elem_nullable || in.i != 0); break;
+      case OP_COL: {
+        // (a lazy gather has no validity of its own until it is forced: its index and its source say)
+        const auto it = std::find(names.begin(), names.end(), p.names[(size_t)in.i]);
+        bool nul = it == names.end();
+        if (!nul) {
+          const ColPtr &c = d.cols[(size_t)(it - names.begin())];
+          nul = c->valid || c->type == Type::Null || (c->lazy && (c->lazy->nullable || c->lazy->src->valid));
+        }
+        st.push_back(nul);
+        break;
+      }
+      case OP_EQ: case OP_NEQ: case OP_LT: case OP_LE: case OP_GT: case OP_GE:
+      case OP_ADD: case OP_SUB: case OP_MUL: {
+        const char b = pop(), a = pop();
+        st.push_back(a || b);
+        break;
+      }
+      case OP_NOT: case OP_NEG: break;
+      case OP_IS_NULL: case OP_IS_NOT_NULL: pop(); st.push_back(0); break;
+      default: return true;
+    }
+  }
+  return st.size() != 1 || st.back();
+}
+
+static LamProg lam_prog(const DeviceProgram &dp) {
+  return LamProg{(const Instr *)dp.code->p, (const ColView *)dp.cols->p, dp.ncode, dp.ncols};
+}
+
+ColPtr list_lambda_column(Session *s, const Data &d, const std::vector<std::string> &names, int32_t kind,
+                          int list_col, const Program &pred, const Program &body, int init_col, Type out) {
+  const int64_t n = d.nrows;
+  const ColPtr &lc = d.cols[(size_t)list_col];
+  const bool quant = kind >= CAPF_LAMBDA_ANY && kind <= CAPF_LAMBDA_SINGLE;
+  const bool has_pred = !pred.code.empty(), has_body = !body.code.empty();
+  if (kind == CAPF_LAMBDA_COMPREHENSION && !has_pred && !has_body) return lc;
+  auto list_of = [&](const BufPtr &off, const ColPtr &child) {
+    auto o = std::make_shared<Column>();
+    o->type = Type::List;
+    o->n = n;
+    o->data = off;
+    o->child = child;
+    o->valid = lc->valid;  // a NULL list gives NULL: the source's validity, shared
+    return o;
+  };
+  auto elements = [&](int64_t m, bool nullable) {
+    return out == Type::Null ? null_column(s, Type::Null, m) : make_column(s, out, m, nullable && m > 0);
+  };
+  if (kind != CAPF_LAMBDA_COMPREHENSION && out == Type::Null) return null_column(s, Type::Null, n);
+  if (n == 0) {  // nothing launches
+    if (kind != CAPF_LAMBDA_COMPREHENSION) return make_column(s, out, 0, true);
+    BufPtr off = s->alloc(8);
+    HIP_CHECK(hipMemsetAsync(off->p, 0, 8, s->stream));
+    return list_of(off, elements(0, false));
+  }
+  force(lc);
+  int64_t total = 0;
+  HIP_CHECK(hipMemcpyAsync(&total, (const int64_t *)lc->data->p + n, 8, hipMemcpyDeviceToHost, s->stream));
+  s->sync();
+  const bool typed = lc->child && lc->child->type != Type::Null;
+  const bool elem_nullable = !typed || lc->child->valid;
+  LamList l{(const int64_t *)lc->data->p, lc->valid ? (const uint8_t *)lc->valid->p : nullptr,
+            ColView{nullptr, nullptr, CAPF_TYPE_NULL, ENC_PLAIN, 0}};
+  if (typed && total > 0) l.e = view_of(lc->child);
+
+  if (kind == CAPF_LAMBDA_REDUCE) {
+    ColPtr o = make_column(s, out, n, true);
+    const ColPtr &ic = d.cols[(size_t)init_col];
+    const ColView init = ic->type == Type::Null ? ColView{nullptr, nullptr, CAPF_TYPE_NULL, ENC_PLAIN, 0} : view_of(ic);
+    DeviceProgram dp = upload_program(s, body, names, d);
+    hipLaunchKernelGGL(k_lam_reduce, dim3(grid_for(n, 256)), dim3(256), 0, s->stream, lam_prog(dp), l, init, n,
+                       (int32_t)out, o->data->p, (uint8_t *)o->valid->p);
+    KERNEL_CHECK();
+    return o;
+  }
+
+  // the predicate's flags, their scan and the kept elements
+  BufPtr pos, kept;
+  int64_t nkept = 0;
+  if (has_pred && total > 0) {
+    BufPtr flag = s->alloc(8 * (total + 1));  // flag[total] = 0: the scan's last entry is the kept total
+    HIP_CHECK(hipMemsetAsync((int64_t *)flag->p + total, 0, 8, s->stream));
+    DeviceProgram dp = upload_program(s, pred, names, d);
+    hipLaunchKernelGGL(k_lam_pred, dim3(grid_for(total, LAM_BLOCK)), dim3(LAM_BLOCK), 0, s->stream, lam_prog(dp), l,
+                       n, total, (int64_t *)flag->p);
+    KERNEL_CHECK();
+    pos = s->alloc(8 * (total + 1));
+    nkept = exclusive_scan_i64(s, (const int64_t *)flag->p, (int64_t *)pos->p, total + 1);
+    if (!quant && nkept > 0 && nkept < total) {
+      kept = s->alloc(8 * nkept);
+      hipLaunchKernelGGL(k_lam_kept, dim3(grid_for(total, 256)), dim3(256), 0, s->stream, (const int64_t *)flag->p,
+                         (const int64_t *)pos->p, total, (int64_t *)kept->p);
+      KERNEL_CHECK();
+    }
+  }
+  if (quant) {
+    ColPtr o = make_column(s, Type::Bool, n, true);
+    hipLaunchKernelGGL(k_lam_rows, dim3(grid_for(n + 1, 256)), dim3(256), 0, s->stream, l.off, l.valid,
+                       pos ? (const int64_t *)pos->p : nullptr, n, kind, (int64_t *)nullptr, (uint8_t *)o->data->p,
+                       (uint8_t *)o->valid->p);
+    KERNEL_CHECK();
+    return o;
+  }
+  BufPtr roff = lc->data;  // without WHERE (or without elements) the source's offsets, shared
+  int64_t m = total;
+  if (has_pred && total > 0) {
+    m = nkept;
+    roff = s->alloc(8 * (n + 1));
+    hipLaunchKernelGGL(k_lam_rows, dim3(grid_for(n + 1, 256)), dim3(256), 0, s->stream, l.off, l.valid,
+                       (const int64_t *)pos->p, n, kind, (int64_t *)roff->p, (uint8_t *)nullptr, (uint8_t *)nullptr);
+    KERNEL_CHECK();
+  }
+  if (m == 0 || out == Type::Null) return list_of(roff, elements(m, false));  // NULL-typed elements move no bytes
+  if (!has_body && m == total) return list_of(roff, lc->child);               // everything kept: the elements, shared
+  DeviceProgram dp;
+  LamProg bp{nullptr, nullptr, 0, 0};
+  if (has_body) {  // (uploaded first: that forces the lazy columns the body reads, so their validity is known)
+    dp = upload_program(s, body, names, d);
+    bp = lam_prog(dp);
+  }
+  ColPtr child = elements(m, has_body ? program_nullable(body, names, d, elem_nullable) : elem_nullable);
+  hipLaunchKernelGGL(k_lam_map, dim3(grid_for(m, LAM_BLOCK)), dim3(LAM_BLOCK), 0, s->stream, bp, l, n,
+                     (const int64_t *)roff->p, kept ? (const int64_t *)kept->p : nullptr, m, (int32_t)out,
+                     child->data->p, child->valid ? (uint8_t *)child->valid->p : nullptr);
+  KERNEL_CHECK();
+  return list_of(roff, child);
 }
 
 // ------------------------------------------------ conjunctive filter fast path

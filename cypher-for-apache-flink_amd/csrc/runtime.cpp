@@ -209,7 +209,7 @@ std::vector<std::string> Program::referenced() const {
 static bool is_numeric(Type t) { return t == Type::Int64 || t == Type::Float64; }
 
 Type infer_type(const Program &p, const std::vector<std::string> &names,
-                const std::vector<Type> &types) {
+                const std::vector<Type> &types, const std::vector<Type> *lambda) {
   std::vector<Type> st;
   bool list_ref = false;
   auto pop = [&]() {
@@ -230,6 +230,11 @@ Type infer_type(const Program &p, const std::vector<std::string> &names,
         st.push_back(types[idx]);
         break;
       }
+      case OP_LAMBDA:  // a lambda slot: only inside a lambda body (capf_table_list_lambda)
+        if (!lambda || in.i < 0 || (size_t)in.i >= lambda->size())
+          illegal("a lambda variable outside the expression that binds it");
+        st.push_back((*lambda)[(size_t)in.i]);
+        break;
       case OP_LIT_INT: st.push_back(Type::Int64); break;
       case OP_LIT_FLOAT: st.push_back(Type::Float64); break;
       case OP_LIT_BOOL: st.push_back(Type::Bool); break;
@@ -706,6 +711,17 @@ static DataPtr materialize_impl(const NodePtr &n) {
       out->cols.push_back(n->types.back() == Type::Null
                               ? null_column(s, Type::Null, c->nrows)
                               : list_fn_column(s, *c, n->list_fn, n->name_cols, n->list_elem));
+      return out;
+    }
+    case Kind::ListLambda: {
+      DataPtr c = materialize(n->kids[0]);
+      auto out = std::make_shared<Data>();
+      out->nrows = c->nrows;
+      out->cols = c->cols;
+      out->cols.push_back(n->types.back() == Type::Null
+                              ? null_column(s, Type::Null, c->nrows)
+                              : list_lambda_column(s, *c, n->kids[0]->names, n->list_fn, n->name_cols[0], n->exprs[0],
+                                                   n->exprs[1], n->name_cols[1], n->list_elem));
       return out;
     }
     case Kind::WithColumns: {
@@ -1991,6 +2007,7 @@ static bool static_list_elem(const NodePtr &n, int i, Type &et, int depth = 0) {
       return true;
     case Kind::ListColumns:
     case Kind::ListFn:
+    case Kind::ListLambda:
       if (i < nk) return static_list_elem(n->kids[0], i, et, depth + 1);
       et = n->list_elem;
       return true;
@@ -2646,6 +2663,71 @@ capf_status capf_table_list_fn(capf_table *t, int32_t fn, int32_t nargs, const c
   }
   nn->names.emplace_back(name);
   nn->types.push_back(out_type);
+  *out = wrap(nn);
+  CAPF_API_END
+}
+
+capf_status capf_table_list_lambda(capf_table *t, int32_t kind, const char *list, const capf_expr *pred,
+                                   const capf_expr *body, const char *init, int32_t out_type, const char *name,
+                                   capf_table **out) {
+  CAPF_API_BEGIN
+  need(t, "table");
+  need(list, "list");
+  need(name, "name");
+  need(out, "out");
+  if (kind < CAPF_LAMBDA_COMPREHENSION || kind > CAPF_LAMBDA_REDUCE) illegal("unknown lambda expression kind");
+  if (out_type < 0 || out_type > 4) illegal("lambda expression result type out of range");
+  const bool quant = kind >= CAPF_LAMBDA_ANY && kind <= CAPF_LAMBDA_SINGLE, reduce = kind == CAPF_LAMBDA_REDUCE;
+  if (quant && !pred) illegal("any / all / none / single need a predicate");
+  if (reduce && (!body || !init || !init[0])) illegal("reduce needs a body and an init column");
+  if (reduce && pred) illegal("reduce takes no predicate");
+  const NodePtr &c = t->node;
+  if (c->col_index(name) >= 0) illegal(std::string("column '") + name + "' already exists");
+  auto nn = new_node(c->s, Kind::ListLambda);
+  nn->kids.push_back(c);
+  nn->names = c->names;
+  nn->types = c->types;
+  nn->list_fn = kind;
+  const int li = c->col_index_or_throw(list);
+  const Type lt = c->types[(size_t)li];
+  if (lt != Type::List && lt != Type::Null)
+    illegal(std::string("a lambda expression over a ") + type_name(lt) + " column, not a LIST");
+  nn->name_cols = {li, reduce ? c->col_index_or_throw(init) : -1};
+  const Type et = lt == Type::List ? list_elem_of(c, li) : Type::Null;
+  if (et == Type::List) not_impl("nested lists");
+  const Type ot = (Type)out_type;
+  nn->exprs.resize(2);
+  if (pred) nn->exprs[0] = Program::from_c(pred);
+  if (body) nn->exprs[1] = Program::from_c(body);
+  auto fits = [](Type got, Type want) {  // a value of type `got` stored as `want`
+    return got == want || got == Type::Null || (got == Type::Int64 && want == Type::Float64);
+  };
+  if (reduce) {
+    const Type it = c->types[(size_t)nn->name_cols[1]];
+    if (it == Type::List) not_impl("reduce with a list accumulator (nested lists)");
+    // the accumulator is typed as the result: init's type, widened or taken from the body
+    nn->lambda_types = {ot, et};
+    const Type bt = infer_type(nn->exprs[1], c->names, c->types, &nn->lambda_types);
+    if (!fits(it, ot) || !fits(bt, ot) || (it != Type::Null && it != ot && !(it == Type::Int64 && bt == Type::Float64)))
+      illegal(std::string("reduce: init is ") + type_name(it) + ", the body " + type_name(bt));
+  } else {
+    nn->lambda_types = {et};
+    if (pred) {
+      const Type pt = infer_type(nn->exprs[0], c->names, c->types, &nn->lambda_types);
+      if (pt != Type::Bool && pt != Type::Null) illegal(std::string("a lambda predicate of type ") + type_name(pt));
+    }
+    if (body) {
+      if (quant) illegal("any / all / none / single take no extract expression");
+      const Type bt = infer_type(nn->exprs[1], c->names, c->types, &nn->lambda_types);
+      if (bt == Type::List) not_impl("nested lists");
+      if (!fits(bt, ot)) illegal(std::string("an extract expression of type ") + type_name(bt) + " declared " + type_name(ot));
+    } else if (!quant && et != ot) {
+      illegal(std::string("a filter over ") + type_name(et) + " elements declared " + type_name(ot));
+    }
+  }
+  nn->list_elem = quant ? Type::Bool : ot;
+  nn->names.emplace_back(name);
+  nn->types.push_back(lt == Type::Null ? Type::Null : quant ? Type::Bool : reduce ? ot : Type::List);
   *out = wrap(nn);
   CAPF_API_END
 }

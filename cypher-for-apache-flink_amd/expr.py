@@ -40,6 +40,7 @@ OP_ROUND, OP_ABS, OP_CEIL, OP_FLOOR, OP_SIGN, OP_SQRT, OP_LOG, OP_LOG10, OP_EXP 
 OP_SIN, OP_COS, OP_TAN, OP_ASIN, OP_ACOS, OP_ATAN, OP_DEGREES, OP_RADIANS = 79, 80, 81, 82, 83, 84, 85, 86
 OP_ATAN2, OP_TO_BOOLEAN, OP_IN_SET, OP_STR_MAP, OP_VALUE_MAP = 87, 88, 89, 90, 91
 OP_STR_TO_NUM, OP_RAND, OP_LIST_INDEX, OP_STR_RANK, OP_STR_MATCH, OP_IN_LIST = 92, 93, 94, 95, 96, 97
+OP_LAMBDA = 98  # push lambda slot iarg (only inside the programs of capf_table_list_lambda)
 NARY_CHUNK = 8   # operands AND / OR / COALESCE take per instruction (longer ones fold in chunks)
 IN_SET_MIN = 17  # list length from which IN runs as a session-set lookup (shorter: an OR of equalities)
 
@@ -667,6 +668,7 @@ def may_hold_list_fn(e):
         return e.__dict__["_lf"]
     except KeyError:
         k = e.__dict__["_lf"] = (isinstance(e, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo))
+                                 or isinstance(e, LAMBDA_EXPRS)
                                  or type(e).__name__ == "Add"
                                  or any(isinstance(x, ListLit) or may_hold_list_fn(x) for x in sub_exprs(e)))
         return k
@@ -678,7 +680,177 @@ def list_valued(e, header, columns, params=None, coltype=None):
     or an Add whose static type is LIST."""
     if isinstance(e, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo)):
         return True
+    if isinstance(e, LAMBDA_EXPRS):  # hoisted too: a LIST temporary, or a scalar one (a quantifier, reduce)
+        return True
     return type(e).__name__ == "Add" and _static_type(e, header, columns, params, coltype) == T_LIST
+
+
+# Lambda expressions over a list (okapi Expr.scala:199 LambdaVar, :1178-1237).
+# Flink's mapper lowers none of them; the semantics are the Morpheus lowering
+# (SparkSQLExprMapper.scala:340-395) on Spark 2.4.3 (build.params.gradle:21):
+# filter / transform / exists / aggregate, with the shared expectations
+# (ExpressionTests.scala:1502-1560, 1575-1643).  The table operations hoist
+# each one into a temporary column built by capf_table_list_lambda (table.py
+# `_hoist_lists`), which runs the expression interpreter once per list ELEMENT
+# with the lambda variable bound (CAPF_OP_LAMBDA).  Below, #T is the number of
+# the row's elements whose predicate is TRUE; a NULL predicate result is not
+# TRUE (Spark 2.4's filter and exists treat it as false).
+#
+# A lambda body may hold literals, parameters, the lambda variable(s), row
+# columns and properties and whatever the interpreter evaluates per row
+# (y IN ys, size(ys), ys[i] over another LIST column included).  A list-valued
+# sub-expression, another lambda expression (nested lists too,
+# ExpressionTests.scala:1562-1572), an aggregator or rand() is NotImplemented.
+# Inside the body the lambda variable shadows a column of its name.
+@dataclass(frozen=True)
+class LambdaVar(Var):
+    """The variable a lambda expression binds (okapi LambdaVar,
+    Expr.scala:199).  Outside its binder it is an IllegalArgumentException."""
+
+
+@dataclass(frozen=True)
+class ListComprehension(Expr):
+    """[variable IN expr WHERE innerPredicate | extractExpression] (okapi
+    ListComprehension, Expr.scala:1178-1189; Morpheus ArrayFilter then
+    ArrayTransform, SparkSQLExprMapper.scala:340-357): the elements whose
+    predicate is TRUE, in order, each mapped through the extract expression.
+    Without WHERE every element; without `|` the element itself (= filter).  A
+    NULL element is bound as NULL: the extract sees NULL, the predicate decides
+    as usual.  A NULL list gives NULL, an empty list [].  The element type is
+    the static type of the extract expression."""
+    variable: Expr
+    innerPredicate: Expr
+    extractExpression: Expr
+    expr: Expr
+
+    def __str__(self):
+        p = "" if self.innerPredicate is None else f" WHERE {self.innerPredicate}"
+        x = "" if self.extractExpression is None else f" | {self.extractExpression}"
+        return f"[{self.variable} IN {self.expr}{p}{x}]"
+
+
+@dataclass(frozen=True)
+class ListReduction(Expr):
+    """reduce(accumulator = initExpr, variable IN list | reduceExpr) (okapi
+    ListReduction, Expr.scala:1191-1201; Morpheus ArrayAggregate,
+    SparkSQLExprMapper.scala:359-369): a left fold in list order.  A NULL list
+    gives NULL, an empty list initExpr; a NULL init or element flows through
+    the body by the interpreter's rules; INTEGER arithmetic wraps as
+    CAPF_OP_ADD.  Type (`reduce_type`): the body's static type with the
+    accumulator typed as init must be init's type (the reference's signature,
+    Expr.scala:1196-1199) — but an INTEGER init with a FLOAT body gives FLOAT
+    (init widened), and a NULL-typed init takes the body's type."""
+    accumulator: Expr
+    variable: Expr
+    reduceExpr: Expr
+    initExpr: Expr
+    list: Expr
+
+    def __str__(self):
+        return f"reduce({self.accumulator} = {self.initExpr}, {self.variable} IN {self.list} | {self.reduceExpr})"
+
+
+def _iterable(name, doc):
+    @dataclass(frozen=True)
+    class _It(Expr):
+        variable: Expr
+        predicate: Expr
+        list: Expr
+
+        def __str__(self):
+            fmt = "filter({} IN {} WHERE {})" if name == "ListFilter" else name[4:].lower() + "(({} IN {} WHERE {}))"
+            return fmt.format(self.variable, self.list, self.predicate)
+    _It.__name__ = _It.__qualname__ = name
+    _It.__doc__ = doc
+    return _It
+
+
+ListFilter = _iterable("ListFilter", """filter(variable IN list WHERE predicate) (okapi ListFilter,
+    Expr.scala:1214-1222; ArrayFilter, SparkSQLExprMapper.scala:346-351): equals
+    [variable IN list WHERE predicate].""")
+ListAny = _iterable("ListAny", """any(variable IN list WHERE predicate) (okapi ListAny, Expr.scala:1224;
+    ArrayExists, SparkSQLExprMapper.scala:384-386): NULL list → NULL, else
+    #T > 0 (empty: FALSE).  Results that are only FALSE or NULL give FALSE, not
+    NULL: Spark 2.4's exists is not three-valued.""")
+ListNone = _iterable("ListNone", """none(variable IN list WHERE predicate) (okapi ListNone, Expr.scala:1228;
+    NOT ArrayExists, SparkSQLExprMapper.scala:387-390): NULL list → NULL, else
+    #T = 0 (empty: TRUE).""")
+ListAll = _iterable("ListAll", """all(variable IN list WHERE predicate) (okapi ListAll, Expr.scala:1232;
+    size(list) = size(filter(list)), SparkSQLExprMapper.scala:379-383): NULL
+    list → NULL (this backend's size of a NULL list is NULL, not Spark's legacy
+    −1), else #T = size(list) (empty: TRUE): a NULL predicate result makes it
+    FALSE.""")
+ListSingle = _iterable("ListSingle", """single(variable IN list WHERE predicate) (okapi ListSingle,
+    Expr.scala:1236; 1 = size(filter(list)), SparkSQLExprMapper.scala:391-394):
+    NULL list → NULL, else #T = 1.""")
+
+LAMBDA_EXPRS = (ListComprehension, ListReduction, ListFilter, ListAny, ListNone, ListAll, ListSingle)
+# CAPF_LAMBDA_*
+LAMBDA_COMPREHENSION, LAMBDA_ANY, LAMBDA_ALL, LAMBDA_NONE, LAMBDA_SINGLE, LAMBDA_REDUCE = 0, 1, 2, 3, 4, 5
+_LAMBDA_KIND = {"ListAny": LAMBDA_ANY, "ListAll": LAMBDA_ALL, "ListNone": LAMBDA_NONE, "ListSingle": LAMBDA_SINGLE}
+
+
+def lambda_parts(e):
+    """(CAPF_LAMBDA_* kind, list operand, predicate, body, init, bound
+    variables in slot order) of a lambda expression; absent parts are None.
+    In reduce slot 0 is the accumulator and slot 1 the element."""
+    if isinstance(e, ListComprehension):
+        return LAMBDA_COMPREHENSION, e.expr, e.innerPredicate, e.extractExpression, None, (e.variable,)
+    if isinstance(e, ListReduction):
+        return LAMBDA_REDUCE, e.list, None, e.reduceExpr, e.initExpr, (e.accumulator, e.variable)
+    if isinstance(e, ListFilter):
+        return LAMBDA_COMPREHENSION, e.list, e.predicate, None, None, (e.variable,)
+    return _LAMBDA_KIND[type(e).__name__], e.list, e.predicate, None, None, (e.variable,)
+
+
+def check_lambda_body(body, owner):
+    """NotImplemented, naming the construct, for what a lambda body may not
+    hold: a list-valued sub-expression, another lambda expression (nested
+    lists), an aggregator or rand()."""
+    from ._lib import NotImplementedException
+
+    def walk(x):
+        what = None
+        if isinstance(x, LAMBDA_EXPRS):
+            what = "a lambda expression inside a lambda body (nested lists)"
+        elif isinstance(x, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo)):
+            what = "a list-valued sub-expression inside a lambda body"
+        elif isinstance(x, ListLit) and x is not body and any(
+                not isinstance(i, (IntegerLit, FloatLit, StringLit, BoolLit, NullLit, Param)) for i in x.items):
+            what = "a list literal of per-row items inside a lambda body"
+        elif isinstance(x, ListLit) and x is body:
+            what = "a list-valued lambda body (nested lists)"
+        elif isinstance(x, Aggregator):
+            what = "an aggregator inside a lambda body"
+        elif isinstance(x, Rand_):
+            what = "rand() inside a lambda body"
+        if what is not None:
+            raise NotImplementedException(f"{what}: {x} in {owner}")
+        for y in sub_exprs(x):
+            walk(y)
+    walk(body)
+
+
+def reduce_type(init_t, body_type):
+    """Result type of reduce: `body_type(t)` is the body's static type with
+    the accumulator typed t (None: unknown)."""
+    from ._lib import IllegalArgumentException, NotImplementedException
+    if init_t == T_NULL:  # a NULL-typed init takes the body's type
+        bt = body_type(T_NULL)
+        if bt is None:
+            bt = next((t for t in (T_INT, T_FLOAT, T_BOOL, T_STRING) if body_type(t) == t), None)
+        if bt is None or bt == T_LIST:
+            raise NotImplementedException("reduce: the type of the body is not known statically")
+        return bt
+    bt = body_type(init_t)
+    if bt is None:
+        raise NotImplementedException("reduce: the type of the body is not known statically")
+    if bt == init_t or bt == T_NULL:
+        return init_t
+    if init_t == T_INT and bt == T_FLOAT:
+        return T_FLOAT  # the INTEGER init widened, as list concatenation widens
+    raise IllegalArgumentException(
+        f"reduce: init is {CAPF_TO_CT[init_t]}, the body {CAPF_TO_CT[bt]} (Expr.scala:1196-1199)")
 
 
 @dataclass(frozen=True)
@@ -1036,13 +1208,63 @@ def _lookups_hold(log, header, columns, params, intern, coltype, lset=None, smap
     return True
 
 
+class _LambdaScope:
+    """The header inside a lambda body: a bound lambda variable — a LambdaVar,
+    or a Var of its name, which it shadows — resolves to a pseudo-column that
+    lowers to CAPF_OP_LAMBDA; everything else to the outer header's answer."""
+
+    def __init__(self, header, lambdas):
+        self.h, self.lam = header, lambdas
+
+    def get(self, e, default=None):
+        if type(e) in (Var, LambdaVar) and e.vname in self.lam:
+            return _LAMBDA_COLS[self.lam[e.vname][0]]
+        return default if self.h is None else self.h.get(e, default)
+
+    def __contains__(self, e):
+        return self.get(e, _MISSING) is not _MISSING
+
+    def items(self):
+        return () if self.h is None else self.h.items()
+
+
+_LAMBDA_COLS = ("\x04lambda0", "\x04lambda1")  # pseudo-columns of the lambda slots
+
+
+def static_type_in_lambda(e, header, columns, params, coltype, lambdas):
+    """`_static_type` of a lambda body: lambdas = {name: (slot, capf type)}."""
+    types = {_LAMBDA_COLS[s]: t for s, t in lambdas.values()}
+    return _static_type(e, _LambdaScope(header, lambdas), set(columns) | set(types), params,
+                        lambda c: types[c] if c in types else coltype(c))
+
+
 def compile_program(expr, header, columns, params=None, intern=None, coltype=None, lset=None, smap=None,
-                    vmap=None):
+                    vmap=None, lambdas=None):
     """Lower `expr` to (ops, iargs, fargs, names) for the C-ABI — memoised per
     expression: a program is reused when every lookup its compilation made
     (header columns, column presence and types, parameters, string codes)
     gives the same answer again (the planner re-plans the same predicates and
-    aggregates query after query).  Programs are immutable once returned."""
+    aggregates query after query).  Programs are immutable once returned.
+
+    lambdas: the bound lambda variables of a lambda body, {name: (slot, capf
+    type)} — each lowers to CAPF_OP_LAMBDA with its slot and shadows a column
+    of its name (not memoised: the program depends on the binding).  A value
+    map (a string function once the dictionary has outgrown a code map,
+    toString, a two-column concatenation) holds the distinct values of a ROW
+    expression: over an operand that holds a lambda variable it is
+    NotImplemented."""
+    if lambdas:
+        types = {_LAMBDA_COLS[s]: t for s, t in lambdas.values()}
+
+        def row_vmap(kind, exprs):  # a value map holds the distinct values of a row expression
+            for x in exprs:
+                if _holds_lambda(x, lambdas):
+                    from ._lib import NotImplementedException
+                    raise NotImplementedException(f"a value map over the lambda variable in {x}")
+            return vmap(kind, exprs)
+        return _compile_program(expr, _LambdaScope(header, lambdas), set(columns) | set(types), params, intern,
+                                lambda c: types[c] if c in types else coltype(c), lset, smap,
+                                row_vmap if vmap is not None else None)
     try:
         key = _memo_key(expr)
     except AttributeError:  # not an Expr instance: compile every time
@@ -1116,10 +1338,15 @@ def _static_type(e, header, columns, params=None, coltype=None):
         return T_BOOL
     if type(e).__name__ in _STR_FUNCS or isinstance(e, (Substring, Replace, ToString)):
         return T_STRING
-    if isinstance(e, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo)):
+    if isinstance(e, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo, ListComprehension, ListFilter)):
         return T_LIST
-    if isinstance(e, (Head, Last)):  # the element type where the column type is known
-        x = e.expr
+    if isinstance(e, (ListAny, ListAll, ListNone, ListSingle)):
+        return T_BOOL
+    # the element type where the column type is known (xs[i] only inside a lambda body, whose
+    # extract expression needs a static type: elsewhere it stays untyped, as it always was)
+    if isinstance(e, (Head, Last)) or (isinstance(e, ContainerIndex) and isinstance(header, _LambdaScope)
+                                       and not (isinstance(e.container, Var) and e.container.ctype == "MAP")):
+        x = e.container if isinstance(e, ContainerIndex) else e.expr
         vals = list_values(x, params) if isinstance(x, (ListLit, Param)) else None
         if vals is not None:
             kinds = {_value_type(v) for v in vals if v is not None}
@@ -1201,7 +1428,10 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
         return name_idx[name]
 
     def col(name):
-        emit(OP_COL, name_of(name))
+        if name in _LAMBDA_COLS:  # a bound lambda variable (_LambdaScope)
+            emit(OP_LAMBDA, _LAMBDA_COLS.index(name))
+        else:
+            emit(OP_COL, name_of(name))
 
     def column_of(e):
         return resolve_column(e, header, columns) if header is not None and e in header else None
@@ -1345,6 +1575,9 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
         cls = type(e).__name__
         if isinstance(e, (Var, HasLabel, HasType, StartNode, EndNode, ElementProperty)):
             c = resolve_column(e, header, columns)
+            if c is None and isinstance(e, LambdaVar):
+                from ._lib import IllegalArgumentException
+                raise IllegalArgumentException(f"lambda variable {e} outside the expression that binds it")
             if c is None:
                 ct = getattr(e, "ctype", "BOOLEAN" if isinstance(e, (HasLabel, HasType)) else "INTEGER")
                 emit(OP_LIT_NULL, CT_TO_CAPF.get(ct, T_NULL))
@@ -1371,6 +1604,8 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
             container_index(ContainerIndex(e.expr, IntegerLit(0 if cls == "Head" else -1)))
         elif cls == "Add" and static_type(e) == T_LIST:
             not_impl(e)  # list concatenation: a table operation (table.py `_hoist_lists`)
+        elif isinstance(e, LAMBDA_EXPRS):
+            not_impl(e)  # a lambda expression: a table operation too (capf_table_list_lambda)
         elif cls == "Add" and T_STRING in (static_type(e.lhs), static_type(e.rhs)):
             # string concatenation (:120-128): concat with the other side cast to
             # STRING; on the GPU one side must be a literal (a code map of the other)
@@ -1790,6 +2025,13 @@ def aggregators_in(e):
         if isinstance(e.default, Expr):
             out += aggregators_in(e.default)
     return out
+
+
+def _holds_lambda(e, lambdas):
+    """Does e hold a variable that `lambdas` binds?"""
+    if type(e) in (Var, LambdaVar):
+        return e.vname in lambdas
+    return any(_holds_lambda(x, lambdas) for x in sub_exprs(e))
 
 
 def replace_exprs(e, m):

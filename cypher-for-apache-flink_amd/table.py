@@ -314,11 +314,11 @@ CODE_MAP_MAX = 1 << 16
 _SELECT_ARGS = {}
 
 
-def _program(expr, header, table, params):
+def _program(expr, header, table, params, lambdas=None):
     return compile_program(expr, header, set(table.physicalColumns), params, table.session.intern,
                            table._coltype, getattr(table.session, "literal_set", None),
                            getattr(table.session, "string_map", None),
-                           lambda kind, exprs: table._value_map(kind, exprs, header, params))
+                           lambda kind, exprs: table._value_map(kind, exprs, header, params), lambdas=lambdas)
 
 
 class GpuTable:
@@ -727,13 +727,20 @@ class GpuTable:
     def _hoist_lists(self, exprs, header, params):
         """(table, exprs', header', temporaries): every list-valued
         sub-expression of `exprs` (expr.list_valued — Reverse, Range, a slice,
-        a concatenating Add — and a list literal of non-literal items below the
-        top of an expression; callers ask expr.may_hold_list_fn first)
-        projected to a temporary LIST column of this table, innermost first,
-        and replaced by a Var of that column (replace_exprs).  Literal
-        arguments become columns through withColumns; capf_table_list_fn builds
-        the list.  Without such a sub-expression nothing changes."""
-        from .expr import ListLit, list_fn_args, list_valued, list_values, replace_exprs, sub_exprs
+        a concatenating Add, a lambda expression — and a list literal of
+        non-literal items below the top of an expression; callers ask
+        expr.may_hold_list_fn first) projected to a temporary column of this
+        table, innermost first, and replaced by a Var of that column
+        (replace_exprs).  Literal arguments become columns through
+        withColumns; capf_table_list_fn builds the list.  A lambda expression
+        (a comprehension, filter, any / all / none / single, reduce) has its
+        list operand hoisted like any other, its init made a column, its
+        predicate / body compiled against the table's columns with the lambda
+        variable bound, and capf_table_list_lambda builds the temporary: a
+        LIST for a comprehension or filter, a scalar for a quantifier or
+        reduce.  Without such a sub-expression nothing changes."""
+        from .expr import (LAMBDA_EXPRS, ListLit, check_lambda_body, lambda_parts, list_fn_args, list_valued,
+                           list_values, replace_exprs, sub_exprs)
         t, h, m, tmps = self, header, {}, []
         cols = set(self.physicalColumns)
 
@@ -743,8 +750,17 @@ class GpuTable:
             return list_valued(e, header, cols, params, self._coltype)
 
         def visit(e, top, found):
-            for x in sub_exprs(e):
-                visit(x, False, found)
+            if isinstance(e, LAMBDA_EXPRS):  # the operand and init are row expressions; the bodies are not
+                _, lst, pred, body, init, _ = lambda_parts(e)
+                for b in (pred, body):
+                    if b is not None:
+                        check_lambda_body(b, e)
+                for x in (lst, init):
+                    if x is not None:
+                        visit(x, False, found)
+            else:
+                for x in sub_exprs(e):
+                    visit(x, False, found)
             if hoistable(e, top) and e not in found:
                 found.append(e)
 
@@ -758,31 +774,83 @@ class GpuTable:
             tmps.append(f"\x03lf{len(tmps)}")
             return tmps[-1]
 
+        def column_of(a):
+            """The column holding argument a: its own, or a new temporary."""
+            nonlocal t
+            ac = h.get(a) if h is not None else None
+            if ac is not None and ac in t.physicalColumns:
+                return ac
+            # a literal, a parameter or a scalar expression: a column of its own
+            name = tmp()
+            t = t.withColumns((a, name), header=h, params=params)
+            return name
+
         for e in found:  # innermost first: the inner ones are columns already
             e2 = replace_exprs(e, m)
             c = tmp()
+            ctype = "LIST"
             if isinstance(e2, ListLit):
                 t = t.withColumns((e2, c), header=h, params=params)
+            elif isinstance(e2, LAMBDA_EXPRS):
+                _, lst, _, _, init, _ = lambda_parts(e2)
+                list_col = column_of(lst)
+                init_col = "" if init is None else column_of(init)
+                t, ctype = t._list_lambda(e2, c, h, params, list_col, init_col)
             else:
                 fn, args = list_fn_args(e2)
-                names = []
-                for a in args:
-                    ac = None if a is None else h.get(a) if h is not None else None
-                    if a is None:
-                        names.append("")
-                    elif ac is not None and ac in t.physicalColumns:
-                        names.append(ac)
-                    else:  # a literal, a parameter or a scalar expression: a column of its own
-                        names.append(tmp())
-                        t = t.withColumns((a, names[-1]), header=h, params=params)
+                names = ["" if a is None else column_of(a) for a in args]
                 t = t._new("capf_table_list_fn", t._h, int(fn), len(names), _lib.strs(names), c.encode())
-            v = Var(c, "LIST")
+            v = Var(c, ctype)
             m[e] = v
             if h is None:
                 from .header import RecordHeader
                 h = RecordHeader({})
             h = h.with_expr(v, c) if hasattr(h, "with_expr") else {**h, v: c}
         return t, [replace_exprs(e, m) for e in exprs], h, tmps
+
+    def _list_lambda(self, e, name, header, params, list_col, init_col):
+        """(this table plus column `name` = the lambda expression e over LIST
+        column list_col, the column's Cypher type): capf_table_list_lambda
+        with the predicate / body compiled with the lambda variable(s) bound —
+        slot 0 the element; in reduce slot 0 the accumulator, slot 1 the
+        element — and the result type worked out here (expr.reduce_type; a
+        comprehension's element type is its extract expression's static
+        type, a filter's the list's)."""
+        from .expr import LAMBDA_COMPREHENSION, LAMBDA_REDUCE, lambda_parts, reduce_type, static_type_in_lambda
+        kind, _, pred, body, _, variables = lambda_parts(e)
+        for v in variables:
+            if not isinstance(v, Var):
+                raise _lib.IllegalArgumentException(f"{v} is not a variable in {e}")
+        et = self.list_elem_type(list_col) if self.capf_type(list_col) == T_LIST else T_NULL
+        if et == T_LIST:
+            raise _lib.NotImplementedException(f"nested lists in {e}")
+        cols = set(self.physicalColumns)
+
+        def body_type(x, lam):
+            return static_type_in_lambda(x, header, cols, params, self._coltype, lam)
+
+        if kind == LAMBDA_REDUCE:
+            acc, x = variables[0].vname, variables[1].vname
+            out = reduce_type(self.capf_type(init_col), lambda at: body_type(body, {acc: (0, at), x: (1, et)}))
+            lam = {acc: (0, out), x: (1, et)}
+        else:
+            lam = {variables[0].vname: (0, et)}
+            out = T_BOOL if kind != LAMBDA_COMPREHENSION else et if body is None else body_type(body, lam)
+            if out is None or out == T_LIST:
+                raise _lib.NotImplementedException(
+                    f"the extract expression of {e}: " + ("nested lists" if out == T_LIST else "its type is not known"))
+        pe = be = None
+        keep = []
+        if pred is not None:
+            pe, k = _lib._keepalive_expr(_program(pred, header, self, params, lam))
+            keep.append(k)
+        if body is not None:
+            be, k = _lib._keepalive_expr(_program(body, header, self, params, lam))
+            keep.append(k)
+        t = self._new("capf_table_list_lambda", self._h, int(kind), list_col.encode(),
+                      None if pe is None else byref(pe), None if be is None else byref(be), init_col.encode(),
+                      int(out), name.encode())
+        return t, ("LIST" if kind == LAMBDA_COMPREHENSION else CAPF_TO_CT[out])
 
     def withColumns(self, *columns, header=None, params=None):
         for e, _ in columns:
@@ -800,6 +868,8 @@ class GpuTable:
             keep = list(t.physicalColumns)
             for i, (e, c) in enumerate(lit):
                 items = _list_items(e, params)
+                if any(_list_items(x, params) is not None for x in items):
+                    raise _lib.NotImplementedException(f"nested lists: {e}")
                 tmp = [f"\x03le{i}.{j}" for j in range(len(items))]
                 if items:
                     t = t.withColumns(*zip(items, tmp), header=header, params=params)

@@ -251,7 +251,13 @@ enum {
    * to x (CAPF_OP_EQ's equality, INTEGER and FLOAT numerically) TRUE;
    * otherwise NULL when the list holds a NULL element, else FALSE.  An element
    * type that cannot equal x's type gives NULL.                              */
-  CAPF_OP_IN_LIST = 97
+  CAPF_OP_IN_LIST = 97,
+  /* The bound variable of a lambda expression (okapi LambdaVar,
+   * Expr.scala:199): pushes lambda slot iarg (0 or 1) of the evaluation.
+   * Only the programs given to capf_table_list_lambda may hold it: slot 0 is
+   * the list element (REDUCE: the accumulator), slot 1 REDUCE's element.
+   * Anywhere else it is IllegalArgument.                                      */
+  CAPF_OP_LAMBDA = 98
 };
 
 typedef struct capf_expr {
@@ -773,6 +779,49 @@ capf_status capf_table_list_columns(capf_table *t, int32_t n, const char *const 
 enum { CAPF_LIST_FN_SLICE = 0, CAPF_LIST_FN_REVERSE = 1, CAPF_LIST_FN_CONCAT = 2, CAPF_LIST_FN_RANGE = 3 };
 capf_status capf_table_list_fn(capf_table *t, int32_t fn, int32_t nargs, const char *const *args,
                                const char *name, capf_table **out);
+/* Lambda expressions over a list (okapi Expr.scala:199 LambdaVar, :1178-1237
+ * ListComprehension / ListReduction / ListFilter / ListAny / ListNone /
+ * ListAll / ListSingle; Flink's mapper lowers none of them — the semantics are
+ * the Morpheus lowering, SparkSQLExprMapper.scala:340-395, on Spark 2.4.3
+ * (build.params.gradle:21): filter / transform / exists / aggregate;
+ * expectations ExpressionTests.scala:1502-1560, 1575-1643).  This table plus
+ * column `name`.  `list` is a LIST column of t; `pred` and `body` are programs
+ * over t's columns that may hold CAPF_OP_LAMBDA; they run once per list
+ * ELEMENT, columns and list opcodes read at the row that owns the element.
+ * #T = the number of the row's elements whose `pred` is TRUE (a NULL result
+ * is not TRUE: Spark 2.4's filter and exists treat it as false):
+ *   COMPREHENSION [x IN xs WHERE pred | body]: the elements with pred TRUE, in
+ *           order, each mapped through body.  pred NULL: every element.  body
+ *           NULL: the element itself (filter(x IN xs WHERE pred)).  A NULL
+ *           element is bound as NULL.  A NULL list gives NULL, an empty list
+ *           [].  out_type = the element type of the result (body's type, else
+ *           the list's element type); element validity exists only when body
+ *           (or the source element) can be NULL.
+ *   ANY     #T > 0 (empty: FALSE)        NONE    #T = 0 (empty: TRUE)
+ *   ALL     #T = size(xs) (empty: TRUE; a NULL pred result makes it FALSE)
+ *   SINGLE  #T = 1
+ *           A NULL list gives NULL for all four: ALL and SINGLE compare
+ *           size(xs), which is NULL here (CAPF_OP_LIST_SIZE), not Spark's -1.
+ *   REDUCE  reduce(acc = init, x IN xs | body): a left fold in list order,
+ *           slot 0 the accumulator, slot 1 the element; `init` is a column of
+ *           t.  A NULL list gives NULL, an empty list init.  NULLs flow
+ *           through body by the interpreter's rules; INTEGER arithmetic wraps
+ *           as CAPF_OP_ADD.  out_type = the result type: init's type when body
+ *           (with the accumulator typed so) gives it; FLOAT for an INTEGER
+ *           init with a FLOAT body (init widened); body's for a NULL-typed
+ *           init; any other mix is IllegalArgument (Expr.scala:1196-1199).
+ * The node is lazy and type-checked when built: `list` must be a LIST or
+ * NULL-typed column (a NULL-typed one gives a NULL-typed column), a
+ * quantifier needs `pred`, REDUCE needs `body` and `init` (else `init` is "").
+ * Nested lists are NotImplemented.                                           */
+enum { CAPF_LAMBDA_COMPREHENSION = 0, CAPF_LAMBDA_ANY = 1, CAPF_LAMBDA_ALL = 2,
+       CAPF_LAMBDA_NONE = 3, CAPF_LAMBDA_SINGLE = 4, CAPF_LAMBDA_REDUCE = 5 };
+capf_status capf_table_list_lambda(capf_table *t, int32_t kind, const char *list,
+                                   const capf_expr *pred,  /* NULL: no WHERE            */
+                                   const capf_expr *body,  /* NULL: no extract / n.a.   */
+                                   const char *init,       /* REDUCE: column name, else "" */
+                                   int32_t out_type,       /* element / result capf type */
+                                   const char *name, capf_table **out);
 /* labels(n) / keys(n) (FlinkSQLExprMapper.scala:136-153; the GetLabels /
  * GetKeys UDFs, :310-329): appends LIST<STRING> column `name` holding, per row,
  * codes[j] for each column cols[j] that holds TRUE (kinds[j] = 0, a label flag)

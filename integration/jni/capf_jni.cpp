@@ -29,6 +29,7 @@
 #include <jni.h>
 
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -582,6 +583,17 @@ JNI(jlong, tableListFn)(JNIEnv *env, jobject, jlong t, jint fn, jobjectArray arg
   JStr nm(env, name);
   capf_table *out = nullptr;
   return fail(env, capf_table_list_fn(T(t), (int32_t)fn, a.n(), a.data(), nm.p, &out)) ? 0 : H(out);
+}
+// a lambda expression over a LIST column (okapi Expr.scala:199, 1178-1237); pred / body null = absent
+JNI(jlong, tableListLambda)(JNIEnv *env, jobject, jlong t, jint kind, jstring list, jobject pred, jobject body,
+                            jstring init, jint outType, jstring name) {
+  JStr l(env, list), in(env, init), nm(env, name);
+  std::unique_ptr<Program> p(pred ? new Program(env, pred) : nullptr), b(body ? new Program(env, body) : nullptr);
+  capf_table *out = nullptr;
+  return fail(env, capf_table_list_lambda(T(t), (int32_t)kind, l.p, p ? &p->e : nullptr, b ? &b->e : nullptr, in.p,
+                                          (int32_t)outType, nm.p, &out))
+             ? 0
+             : H(out);
 }
 JNI(jlong, tableWithColumns)(JNIEnv *env, jobject, jlong t, jobjectArray exprs,
                              jobjectArray names) {  // Table.scala:170

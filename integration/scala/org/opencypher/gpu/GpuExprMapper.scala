@@ -50,7 +50,10 @@ object GpuExprMapper {
   private final val ContainsKind = Native.StrMatchContains.toLong
   private final val InSetMin = 17 // IN lists from this length: one set lookup per row (expr.py IN_SET_MIN)
 
-  def program(expr: Expr, header: RecordHeader, table: GpuTable, parameters: CypherMap): Program = {
+  /** `lambdas`: the bound lambda variables of a lambda body (name -> slot; GpuTable.hoistLists) —
+    * each lowers to CAPF_OP_LAMBDA with its slot and shadows a column of its name. */
+  def program(expr: Expr, header: RecordHeader, table: GpuTable, parameters: CypherMap,
+              lambdas: Map[String, Int] = Map.empty): Program = {
     val ops = mutable.ArrayBuffer.empty[Int]
     val iargs = mutable.ArrayBuffer.empty[Long]
     val fargs = mutable.ArrayBuffer.empty[Double]
@@ -125,6 +128,12 @@ object GpuExprMapper {
     // JVM's casts (Long.toString / Double.toString) of each, concatenated, interned
     // (the shim's twin of table.py GpuTable._value_map)
     def valueMap(xs: Seq[Expr], regex: Option[String] = None, fn: Option[Seq[Any]] = None): String = {
+      // a value map holds the distinct values of a ROW expression: none over a lambda variable
+      def holdsLambda(e: Expr): Boolean = e match {
+        case v: Var => lambdas.contains(v.name)
+        case _ => e.children.exists(holdsLambda)
+      }
+      xs.find(holdsLambda).foreach(x => throw NotImplementedException(s"a value map over the lambda variable in $x"))
       val names = xs.indices.map(i => s"\u0002vm$i")
       val t = table.withColumns(xs.zip(names): _*)(header, parameters).distinct(names: _*)
       if (t.size > (1L << 22))  // every distinct value becomes a host string (table.py VALUE_MAP_MAX)
@@ -220,6 +229,10 @@ object GpuExprMapper {
     }
 
     def go(e: Expr): Unit = e match {
+      // the bound variable of a lambda expression (okapi LambdaVar, Expr.scala:199): its slot;
+      // outside the expression that binds it, an error
+      case v: Var if lambdas.contains(v.name) => emit(Native.OpLambda, lambdas(v.name).toLong)
+      case v: LambdaVar => throw IllegalArgumentException("a bound lambda variable", v)
       case _: Var | _: HasLabel | _: HasType | _: StartNode | _: EndNode | _: ElementProperty =>
         physical(e) match {
           case Some(c) => col(c)

@@ -116,9 +116,31 @@ final class GpuTable private (private[gpu] val handle: Long)(implicit val sessio
     case _ => None
   }
 
-  /** Every list-valued sub-expression (listFnArgs; a list literal of per-row items below
-    * the top) projected to a temporary LIST column, innermost first, and replaced by a
-    * Var of that column: (table, rewritten expressions, header, temporaries). */
+  /** A lambda expression over a list (okapi Expr.scala:199, 1178-1237; the Morpheus lowering
+    * SparkSQLExprMapper.scala:340-395) as (CAPF_LAMBDA_* kind, list operand, predicate, body,
+    * init, bound variables in slot order): table.py `lambda_parts`.  In reduce slot 0 is the
+    * accumulator and slot 1 the element. */
+  private def lambdaParts(e: Expr)
+  : Option[(Int, Expr, Option[Expr], Option[Expr], Option[Expr], Seq[Expr])] = e match {
+    case c: ListComprehension =>
+      Some((Native.LambdaComprehension, c.expr, c.innerPredicate, c.extractExpression, None, Seq(c.variable)))
+    case r: ListReduction =>
+      Some((Native.LambdaReduce, r.list, None, Some(r.reduceExpr), Some(r.initExpr), Seq(r.accumulator, r.variable)))
+    case f: ListFilter => Some((Native.LambdaComprehension, f.list, Some(f.predicate), None, None, Seq(f.variable)))
+    case q: ListAny => Some((Native.LambdaAny, q.list, Some(q.predicate), None, None, Seq(q.variable)))
+    case q: ListAll => Some((Native.LambdaAll, q.list, Some(q.predicate), None, None, Seq(q.variable)))
+    case q: ListNone => Some((Native.LambdaNone, q.list, Some(q.predicate), None, None, Seq(q.variable)))
+    case q: ListSingle => Some((Native.LambdaSingle, q.list, Some(q.predicate), None, None, Seq(q.variable)))
+    case _ => None
+  }
+
+  /** Every list-valued sub-expression (listFnArgs; a lambda expression; a list literal of
+    * per-row items below the top) projected to a temporary column, innermost first, and
+    * replaced by a Var of that column: (table, rewritten expressions, header, temporaries).
+    * A lambda expression has its list operand and init hoisted like any other argument and
+    * its predicate / body compiled with the lambda variables bound
+    * (capf_table_list_lambda); the temporary is a LIST for a comprehension or filter, a
+    * scalar for a quantifier or reduce. */
   private def hoistLists(exprs: Seq[Expr], header: RecordHeader, parameters: CypherMap)
   : (GpuTable, Seq[Expr], RecordHeader, Seq[String]) = {
     var t = this
@@ -130,32 +152,88 @@ final class GpuTable private (private[gpu] val handle: Long)(implicit val sessio
       case ListLit(items) => items.exists(i => !i.isInstanceOf[Lit[_]] && !i.isInstanceOf[Param])
       case _ => false
     }
-    def lower(e: Expr, top: Boolean): Expr = done.getOrElse(e, {
-      val kids = e.children.map(c => lower(c, top = false))
-      val e2 = if (kids.isEmpty || e.isInstanceOf[ListLit]) e else e.withNewChildren(kids.toArray)
-      val col: Option[String] = listFnArgs(e2) match {
-        case Some((fn, args)) =>
-          val names = args.map {
-            case None => ""
-            case Some(a) if h.contains(a) && t.physicalColumns.contains(h.column(a)) => h.column(a)
-            case Some(a) => val c = tmp(); t = t.withColumns(a -> c)(h, parameters); c
-          }
-          val c = tmp()
-          t = wrap(Native.tableListFn(t.handle, fn, names.toArray, c))
-          Some(c)
-        case None if !top && perRowLiteral(e2) =>
-          val c = tmp(); t = t.withColumns(e2 -> c)(h, parameters); Some(c)
-        case None => None
+    def columnFor(a: Expr): String =
+      if (h.contains(a) && t.physicalColumns.contains(h.column(a))) h.column(a)
+      else { val c = tmp(); t = t.withColumns(a -> c)(h, parameters); c }
+    // what a lambda body may not hold (table.py `check_lambda_body`)
+    def checkLambdaBody(x: Expr, owner: Expr): Unit = {
+      val what = x match {
+        case _ if lambdaParts(x).isDefined => Some("a lambda expression inside a lambda body (nested lists)")
+        case _ if listFnArgs(x).isDefined => Some("a list-valued sub-expression inside a lambda body")
+        case _ if perRowLiteral(x) => Some("a list literal of per-row items inside a lambda body")
+        case _: Aggregator => Some("an aggregator inside a lambda body")
+        case Rand => Some("rand() inside a lambda body")
+        case _ => None
       }
-      col match {
-        case Some(c) =>
-          val v = Var(c)(e2.cypherType)
-          h = h.withExpr(v)
-          // the temporary is read under its own name
-          if (h.column(v) != c) t = t.select(t.physicalColumns.map(x => if (x == c) c -> h.column(v) else x -> x): _*)
-          done += e -> v
-          v
-        case None => e2
+      what.foreach(w => throw NotImplementedException(s"$w: $x in $owner"))
+      if (!x.isInstanceOf[ListLit]) x.children.foreach(checkLambdaBody(_, owner))
+    }
+    def lowerLambda(e: Expr, kind: Int, list: Expr, pred: Option[Expr], body: Option[Expr], init: Option[Expr],
+                    variables: Seq[Expr]): String = {
+      import org.opencypher.okapi.api.types._
+      (pred ++ body).foreach(checkLambdaBody(_, e))
+      val listCol = columnFor(lower(list, top = false))
+      val initCol = init.map(i => columnFor(lower(i, top = false))).getOrElse("")
+      val slots = variables.zipWithIndex.map {
+        case (v: Var, i) => v.name -> i
+        case (other, _) => throw IllegalArgumentException("a lambda variable", other)
+      }.toMap
+      val elem = list.cypherType.material match { case CTList(inner) => inner; case _ => CTNull }
+      val outType: CypherType = kind match {
+        case Native.LambdaComprehension => body.map(_.cypherType).getOrElse(elem)
+        case Native.LambdaReduce =>  // init's type; INTEGER with a FLOAT body widens; a NULL init takes the body's
+          (init.get.cypherType.material, body.get.cypherType.material) match {
+            case (CTNull | CTVoid, bt) => bt
+            case (CTInteger, CTFloat) => CTFloat
+            case (it, _) => it
+          }
+        case _ => CTBoolean
+      }
+      if (outType.material.isInstanceOf[CTList]) throw NotImplementedException(s"nested lists in $e")
+      val c = tmp()
+      val predProgram = pred.map(GpuExprMapper.program(_, h, t, parameters, slots)).orNull
+      val bodyProgram = body.map(GpuExprMapper.program(_, h, t, parameters, slots)).orNull
+      t = wrap(Native.tableListLambda(t.handle, kind, listCol, predProgram, bodyProgram, initCol,
+        GpuTypes.fromCypher(outType), c))
+      c
+    }
+    def lower(e: Expr, top: Boolean): Expr = done.getOrElse(e, {
+      val parts = lambdaParts(e)
+      if (parts.isDefined) {
+        val (kind, list, pred, body, init, variables) = parts.get
+        val c = lowerLambda(e, kind, list, pred, body, init, variables)
+        val v = Var(c)(e.cypherType)
+        h = h.withExpr(v)
+        if (h.column(v) != c) t = t.select(t.physicalColumns.map(x => if (x == c) c -> h.column(v) else x -> x): _*)
+        done += e -> v
+        v
+      } else {
+        val kids = e.children.map(c => lower(c, top = false))
+        val e2 = if (kids.isEmpty || e.isInstanceOf[ListLit]) e else e.withNewChildren(kids.toArray)
+        val col: Option[String] = listFnArgs(e2) match {
+          case Some((fn, args)) =>
+            val names = args.map {
+              case None => ""
+              case Some(a) if h.contains(a) && t.physicalColumns.contains(h.column(a)) => h.column(a)
+              case Some(a) => val c = tmp(); t = t.withColumns(a -> c)(h, parameters); c
+            }
+            val c = tmp()
+            t = wrap(Native.tableListFn(t.handle, fn, names.toArray, c))
+            Some(c)
+          case None if !top && perRowLiteral(e2) =>
+            val c = tmp(); t = t.withColumns(e2 -> c)(h, parameters); Some(c)
+          case None => None
+        }
+        col match {
+          case Some(c) =>
+            val v = Var(c)(e2.cypherType)
+            h = h.withExpr(v)
+            // the temporary is read under its own name
+            if (h.column(v) != c) t = t.select(t.physicalColumns.map(x => if (x == c) c -> h.column(v) else x -> x): _*)
+            done += e -> v
+            v
+          case None => e2
+        }
       }
     })
     val out = exprs.map(lower(_, top = true))

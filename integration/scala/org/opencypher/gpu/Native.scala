@@ -67,6 +67,15 @@ object Native {
   final val ListFnReverse = 1
   final val ListFnConcat = 2
   final val ListFnRange = 3
+  // CAPF_OP_LAMBDA (opcode 98): push lambda slot iarg; only in the programs of capf_table_list_lambda
+  final val OpLambda = 98
+  // CAPF_LAMBDA_* kinds of capf_table_list_lambda
+  final val LambdaComprehension = 0
+  final val LambdaAny = 1
+  final val LambdaAll = 2
+  final val LambdaNone = 3
+  final val LambdaSingle = 4
+  final val LambdaReduce = 5
   final val StrMatchStartsWith = 0
   final val StrMatchEndsWith = 1
   final val StrMatchContains = 2
@@ -180,6 +189,9 @@ object Native {
   @native def tableListColumns(table: Long, cols: Array[String], name: String): Long
   // capf_table_list_fn: fn = ListFn*, args = column names ("" = an absent slice bound / step)
   @native def tableListFn(table: Long, fn: Int, args: Array[String], name: String): Long
+  // capf_table_list_lambda: kind = Lambda*, pred / body = null when absent, init = "" but for reduce
+  @native def tableListLambda(table: Long, kind: Int, list: String, pred: Program, body: Program, init: String,
+                              outType: Int, name: String): Long
   @native def tableShow(table: Long, rows: Int): Unit
 
   // graph inputs (EdgeListDataSource.scala:56-92; synthetic R-MAT / node ranges)
