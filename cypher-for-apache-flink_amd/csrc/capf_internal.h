@@ -143,6 +143,10 @@ struct Column {
   mutable int64_t bits_key[2] = {0, 0};
   mutable std::weak_ptr<Column> index_peer;
   mutable int64_t index_key[2] = {0, 0};
+  // the in side of the fused 2-hop count over (this = end(r), peer = start(r)):
+  // per-bucket in-degree images and the self-loop count (C5InIndex,
+  // chain2_partitioned.hip; its key is kept inside it)
+  mutable std::shared_ptr<void> c5_index;
   // provenance of a node-partitioned copy's key column (capf_table_node_partition):
   // every value is a node of [owner[0], owner[0] + owner[1]) owned by part owner[3]
   // of owner[2] — the sharded count then skips its range and ownership tests.
@@ -762,9 +766,20 @@ struct C2Spill {
 // the self-loop total into [1] and clears [0] and [2] itself (no memset needed)
 // spill: non-null → the hand-off log is left for the dot kernel (no separate
 // overflow kernel); null → the overflow kernel runs.
+// ends: non-null when both hops scan the same rel table — the columns behind
+// cols[1] (end(r1), which keeps the in-side index) and cols[0] (start(r1), its
+// peer).  The first query over such a pair stores the in side's images on the
+// column, later ones partition and probe the out side only.
+struct C5IndexCols {
+  ColPtr end, start;
+};
 bool chain2_partitioned(Session *s, const ColView *cols, int64_t n, int64_t lo, int64_t hi,
                         bool in_range, uint32_t *h_in, uint32_t *h_out,
-                        unsigned long long *d_acc3, C2Spill *spill = nullptr);
+                        unsigned long long *d_acc3, C2Spill *spill = nullptr,
+                        const C5IndexCols *ends = nullptr);
+// true: that call would be answered from a Ready in-side index (h_in / h_out unused)
+bool chain2_index_serves(Session *s, const ColView *cols, int64_t n, int64_t lo, int64_t hi, bool in_range,
+                         const C5IndexCols &ends);
 
 }  // namespace capf
 

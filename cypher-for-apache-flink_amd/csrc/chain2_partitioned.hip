@@ -43,8 +43,12 @@
 //         finalised halves through HBM (C5Steal: nobody waits for anybody).
 //         Each unit adds its Σ and its share of the self-loops; the last one
 //         writes the count.
+// Mode I: when both hops scan one rel table, the first query over its column
+// pair stores every bucket's finished image on the end column (C5InIndex); later
+// queries run a one-sided P1 (out keys of the source column, half the bytes) and
+// units that only load images and probe (k_c5_gather<.., PROBE, IDX>).
 // The other modes of the fused count
-// (C5PostPlan; the table of all seven is in DESIGN.md) add
+// (C5PostPlan; the table of all eight is in DESIGN.md) add
 //   T  k_c3_transpose  [tile][run] → [run][tile] meta, per-run totals, Σ self-loops
 //   U  k_c3_units      device work list (one unit per run; hub-heavy runs split)
 //   O  k_c3_overflow   adds the logged hand-offs to the histograms
@@ -236,7 +240,14 @@ __device__ inline int64_t c5_xcd_tile(int64_t b, int64_t g) {
   return b < 8 * per ? (b % 8) * per + b / 8 : b;
 }
 
-template <int W, bool ALIAS, bool CHECK, bool RAGGED, class SH, int UPF = 0>
+// ONE (the indexed 2-hop count: the in side is cached on the column, C5InIndex
+// below): one key per row, the out key of the source column alone — nb runs, no
+// in-runs, no self-loop test, the peer column is never read.  A tile is then
+// 2·TILE rows (rows [e0, e0 + TILE) take the place of the source column's
+// loads, rows [e0 + TILE, e0 + 2·TILE) that of the target column's), so the
+// stage, the 2·RPT keys per thread and the schedule are those of the two-sided
+// tile.
+template <int W, bool ALIAS, bool CHECK, bool RAGGED, class SH, int UPF = 0, bool ONE = false>
 // Self-loops go out as one plain uint32 per tile (tile_loops[t], summed by
 // k_c3_units); every tile's workgroup also clears its share of the `zwords` words at zbuf
 // (the run totals / work-list header of the post-P1 kernels) — no memset
@@ -255,7 +266,9 @@ __global__ __launch_bounds__(C5_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) v
   __shared__ uint32_t lds_scan[17];
   uint16_t *stage = (uint16_t *)stage4;
   const int64_t t = t_base + (run_major && !RAGGED ? c5_xcd_tile(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x);
-  const int nr = 2 * c.nb;
+  static_assert(!ONE || ALIAS, "one-sided tiles read the r1 columns");
+  constexpr int ROWS = ONE ? 2 * TILE : TILE;  // rows per tile
+  const int nr = ONE ? c.nb : 2 * c.nb;
   // pad keys: 8·(t mod 8) + slot-in-piece (P3 subtracts them per bin)
   const uint32_t pb = 8u * (uint32_t)(t & 7);
   const uint4 pad = make_uint4(pb | (pb + 1) << 16, (pb + 2) | (pb + 3) << 16,
@@ -268,9 +281,9 @@ __global__ __launch_bounds__(C5_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) v
   }
   if (t == 0 && zacc && threadIdx.x < 3) zacc[threadIdx.x] = 0;  // [Σ, loops, done]
   __syncthreads();
-  const int64_t e0 = t * TILE;
-  const int64_t e1 = RAGGED ? min(e0 + TILE, c.n) : e0 + TILE;
-  const uint32_t out_run0 = (uint32_t)c.nb << C2_BITS;
+  const int64_t e0 = t * ROWS;
+  const int64_t e1 = RAGGED ? min(e0 + ROWS, c.n) : e0 + ROWS;
+  const uint32_t out_run0 = ONE ? 0u : (uint32_t)c.nb << C2_BITS;
   const uint32_t dummy = (uint32_t)nr << C2_BITS;
   uint32_t kin[RPT], kout[RPT];
   uint32_t lp = 0;
@@ -281,9 +294,10 @@ __global__ __launch_bounds__(C5_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) v
     for (int g = 0; g < GROUPS; ++g) {
       const int64_t e = e0 + 4 * ((int64_t)g * C5_BLOCK + threadIdx.x);
       ru[g] = c5_ld_raw<W, UPF >= 2>((const uint8_t *)c.u1 + W * e);
-      rv[g] = c5_ld_raw<W, UPF >= 2>((const uint8_t *)c.v1 + W * e);
+      rv[g] = ONE ? c5_ld_raw<W, UPF >= 2>((const uint8_t *)c.u1 + W * (e + TILE))
+                  : c5_ld_raw<W, UPF >= 2>((const uint8_t *)c.v1 + W * e);
     }
-    const uint32_t du = (uint32_t)(c.bu1 - c.lo), dv = (uint32_t)(c.bv1 - c.lo);
+    const uint32_t du = (uint32_t)(c.bu1 - c.lo), dv = ONE ? du : (uint32_t)(c.bv1 - c.lo);
     // D0 (UPF 3: FOR bases = lo, 24-bit multiply): offsets are the raw fields —
     // __umul24 reads only the low 24 bits, so no mask and no add; the self-loop
     // test compares the mixed keys (node_mix is a bijection on [0, 2^k))
@@ -309,10 +323,12 @@ __global__ __launch_bounds__(C5_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) v
         const int j = 4 * g + k;
         kin[j] = node_mix_t<SH::WIDE>(y1[k], c.mix);
         kout[j] = node_mix_t<SH::WIDE>(x1[k], c.mix) + out_run0;
-        if constexpr (D0)
-          lp += kout[j] - kin[j] == out_run0 ? 1u : 0u;
-        else
-          lp += y1[k] == x1[k] ? 1u : 0u;
+        if constexpr (!ONE) {  // (ONE: both keys are out keys, of different rows)
+          if constexpr (D0)
+            lp += kout[j] - kin[j] == out_run0 ? 1u : 0u;
+          else
+            lp += y1[k] == x1[k] ? 1u : 0u;
+        }
         atomicAdd(&cur[kin[j] >> C2_BITS], 1u);
         atomicAdd(&cur[kout[j] >> C2_BITS], 1u);
       }
@@ -327,7 +343,10 @@ __global__ __launch_bounds__(C5_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) v
   if (ALIAS && !UPFRONT) {
     const int64_t e = e0 + 4 * (int64_t)threadIdx.x;
     c5_load4<W, CHECK>(c.u1, c.bu1, c.lo, c.len, e, e1, RAGGED, px[0], pox[0]);
-    c5_load4<W, CHECK>(c.v1, c.bv1, c.lo, c.len, e, e1, RAGGED, py[0], poy[0]);
+    if constexpr (ONE)
+      c5_load4<W, CHECK>(c.u1, c.bu1, c.lo, c.len, e + TILE, e1, RAGGED, py[0], poy[0]);
+    else
+      c5_load4<W, CHECK>(c.v1, c.bv1, c.lo, c.len, e, e1, RAGGED, py[0], poy[0]);
   }
 #pragma unroll
   for (int g = 0; g < (UPFRONT ? 0 : GROUPS); ++g) {
@@ -338,7 +357,10 @@ __global__ __launch_bounds__(C5_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) v
       if (g + 1 < GROUPS) {
         const int64_t en = e + 4 * C5_BLOCK;
         c5_load4<W, CHECK>(c.u1, c.bu1, c.lo, c.len, en, e1, RAGGED, px[(g + 1) & 1], pox[(g + 1) & 1]);
-        c5_load4<W, CHECK>(c.v1, c.bv1, c.lo, c.len, en, e1, RAGGED, py[(g + 1) & 1], poy[(g + 1) & 1]);
+        if constexpr (ONE)
+          c5_load4<W, CHECK>(c.u1, c.bu1, c.lo, c.len, en + TILE, e1, RAGGED, py[(g + 1) & 1], poy[(g + 1) & 1]);
+        else
+          c5_load4<W, CHECK>(c.v1, c.bv1, c.lo, c.len, en, e1, RAGGED, py[(g + 1) & 1], poy[(g + 1) & 1]);
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -358,15 +380,16 @@ __global__ __launch_bounds__(C5_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) v
       const int j = 4 * g + k;
       const uint32_t b = y1[k];                   // end(r1)
       const uint32_t cq = ALIAS ? x1[k] : x2[k];  // start(r2)
-      const bool in_ok = okx1[k] & oky1[k];       // start(r1) ∈ S_a, end(r1) ∈ S_b
-      const bool out_ok = ALIAS ? in_ok : (okx2[k] & oky2[k]);
+      // (ONE: b and cq are the sources of two different rows, each its own out key)
+      const bool in_ok = ONE ? oky1[k] : (okx1[k] & oky1[k]);  // start(r1) ∈ S_a, end(r1) ∈ S_b
+      const bool out_ok = ONE ? okx1[k] : ALIAS ? in_ok : (okx2[k] & oky2[k]);
       kin[j] = node_mix_t<SH::WIDE>(b, c.mix);
       kout[j] = node_mix_t<SH::WIDE>(cq, c.mix) + out_run0;
       if (CHECK || RAGGED) {
         kin[j] = in_ok ? kin[j] : dummy;
         kout[j] = out_ok ? kout[j] : dummy;
       }
-      lp += (in_ok & out_ok & (b == cq)) ? 1u : 0u;
+      if constexpr (!ONE) lp += (in_ok & out_ok & (b == cq)) ? 1u : 0u;
       // count only (no return: no wait); positions come from a second pass
       atomicAdd(&cur[kin[j] >> C2_BITS], 1u);
       atomicAdd(&cur[kout[j] >> C2_BITS], 1u);
@@ -413,7 +436,7 @@ __global__ __launch_bounds__(C5_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) v
   // the stage IS the region's layout: contiguous 16-B copy-out
   uint4 *dst = (uint4 *)(part + t * c.rstride);
   for (uint32_t i = threadIdx.x; i < total / 8; i += C5_BLOCK) dst[i] = stage4[i];
-  c5_tile_sum(lp, lds_scan, tile_loops + t);
+  if constexpr (!ONE) c5_tile_sum(lp, lds_scan, tile_loops + t);
 }
 
 // [tile][run] → [run][tile] and per-run totals.  A block moves 32 runs ×
@@ -656,6 +679,7 @@ struct C5Probe {
   const uint32_t *tile_loops;  // P1's per-tile self-loop counts
   uint32_t hotcap;             // hot-table slots in use (1..C5_HOT; CAPF_C5_HOTCAP: tests)
   C5Steal st;
+  const unsigned long long *idx_loops = nullptr;  // indexed units: the self-loop count kept with the images
 };
 
 // the unit's job mailbox in LDS (words)
@@ -765,7 +789,15 @@ __device__ inline int64_t uniform64(int64_t v) {
 // Phase 2 is a loop over jobs — the unit's own out-run, then tile ranges of the
 // out-runs of published buckets, each against that bucket's image loaded into
 // this unit's LDS (C5Steal above) — with ONE inlined walk(probe) in it.
-template <int PPS, bool PROBE = false>
+//
+// IDX (mode P over a C5InIndex, below): the images of all nb buckets were stored
+// by an earlier query, so a unit has no phase 1, no finalise, no hot table and
+// nothing to publish.  Slot s is a finished image from the start (read-only data
+// of an earlier kernel: no flag, no acquire); unit b starts in the job loop on
+// slot b's cursor, then scans the other cursors as any helper does — the reload
+// path minus everything in front of the load.  The out-runs are runs [0, nb) of
+// a one-sided P1; the self-loop count comes from the index.
+template <int PPS, bool PROBE = false, bool IDX = false>
 __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
                                                             const int32_t *nunits,
                                                             const uint16_t *part,
@@ -813,12 +845,15 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
   uint32_t *hist = side ? h_out : h_in;
   const uint32_t log_base = (uint32_t)((int64_t)(u.run % nb) * C2_BW);  // packed: side bin of key 0
   const uint32_t hist_base = (uint32_t)(u.slice * slice_stride + (int64_t)(u.run % nb) * C2_BW);
-  for (int i = threadIdx.x; i < C2_WORDS + C5_CORR; i += C5_BLOCK) words[i] = 0;
+  static_assert(!IDX || PROBE, "an index is probed");
+  if constexpr (!IDX)
+    for (int i = threadIdx.x; i < C2_WORDS + C5_CORR; i += C5_BLOCK) words[i] = 0;
   if constexpr (PROBE) {
-    for (int i = threadIdx.x; i < C5_HOT; i += C5_BLOCK) {
-      hk[i] = C5_HOT_EMPTY;
-      hv[i] = 0;
-    }
+    if constexpr (!IDX)
+      for (int i = threadIdx.x; i < C5_HOT; i += C5_BLOCK) {
+        hk[i] = C5_HOT_EMPTY;
+        hv[i] = 0;
+      }
     if (threadIdx.x < C5_CORR) corr_out[threadIdx.x] = 0;
     if (threadIdx.x < 3) nspec[threadIdx.x] = 0;  // + hotpad[0..1]
     if (threadIdx.x < CJ_WORDS) job[threadIdx.x] = 0;
@@ -859,7 +894,7 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
   const uint4 dead_keys = make_uint4(lane | lane << 16, lane | lane << 16, lane | lane << 16,
                                      lane | lane << 16);
   // batch setup: table of tiles [tb, tb + 64) into tab2[buf]; returns the piece total
-  uint32_t wpre = w0 + lane < w1 ? m[(w0 + lane) * mstride] : 0u;  // meta word of the next batch
+  uint32_t wpre = !IDX && w0 + lane < w1 ? m[(w0 + lane) * mstride] : 0u;  // meta word of the next batch
   auto setup = [&](int64_t tb, int buf) -> uint32_t {
     const int64_t t = tb + lane;
     const uint32_t w = wpre;
@@ -1078,9 +1113,22 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
       if (padc[e]) atomicAdd(&cb[pcls + e], padc[e]);
     if (dead) atomicAdd(&cb[lane], 8 * dead);
   };
-  walk(count);
-  flush_corr(corr);
+  if constexpr (!IDX) {
+    walk(count);
+    flush_corr(corr);
+  } else {
+    (void)count;
+  }
   if constexpr (PROBE) {
+    uint16_t *halves = (uint16_t *)words;
+    if constexpr (IDX) {
+      if (threadIdx.x == 0) {  // slot ui's cursor first; no image in LDS yet
+        job[CJ_CUR] = ui;
+        job[CJ_IMG] = CJ_NONE;
+        job[CJ_MINE] = ui;
+        job[CJ_BKT] = ui;
+      }
+    } else {
     __syncthreads();
     // Finalise: every half is < 2^15 now and nothing adds any more, so a half
     // may use all 16 bits.  A hot key's total T (slot total + remainder − its
@@ -1127,7 +1175,6 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
     // Re-lay the halves as one uint16 per key (halves[key]): the probe's LDS
     // address is then key·2, two VALU instead of five.  Through registers: every
     // thread holds its 32 words across the barrier.
-    uint16_t *halves = (uint16_t *)words;
     {
       uint32_t wr[C2_WORDS / C5_BLOCK];
 #pragma unroll
@@ -1196,6 +1243,7 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
       job[CJ_IMG] = my_image && st->steal != C5_STEAL_RELOAD ? job[CJ_MINE] : CJ_OWN;
       job[CJ_BKT] = u.run;
     }
+    }  // !IDX
     // the image in LDS: its special keys' count and its bucket's first log key
     uint32_t ns = 0, pbase = log_base;
     // in[key] in full (cold: the pad-bin correction below)
@@ -1252,6 +1300,8 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
           wsum += (unsigned long long)cn * (uint32_t)__builtin_amdgcn_readfirstlane((int)sx[i]);
         }
       }
+      // (IDX: never taken — an index holds no logged key.  Kept: compiled out, the
+      // walk's schedule changes and 11 VGPRs spill, 48 B of scratch per lane)
       if (__builtin_amdgcn_ballot_w64(mx == 0xFFFFu) != 0) {
         // (hot table full) keys whose counts are in the global log: one copy of the scan
         uint32_t lm = 0;
@@ -1304,11 +1354,13 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
           }
           if (found < 0) {
             const uint32_t nsl =
-                min(__hip_atomic_load(sb->slots_used, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), sb->nslots);
+                IDX ? sb->nslots
+                    : min(__hip_atomic_load(sb->slots_used, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), sb->nslots);
             for (uint32_t s0 = 0; s0 < nsl && found < 0; s0 += WAVE) {
               const uint32_t sl = s0 + lane;
               bool cand = sl < nsl;
-              if (cand) cand = __hip_atomic_load(&sb->ready[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+              if (!IDX && cand)
+                cand = __hip_atomic_load(&sb->ready[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
               if (cand) cand = __hip_atomic_load(&sb->cursor[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < njobs;
               unsigned long long mask = __builtin_amdgcn_ballot_w64(cand);
               while (mask && found < 0) {
@@ -1322,7 +1374,7 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
           }
         }
         const bool need = found >= 0 && found != jb[CJ_IMG];
-        if (need) {  // the slot's flag was read set: ONE agent-scope acquire, in front of the barrier
+        if (!IDX && need) {  // the slot's flag was read set: ONE agent-scope acquire, in front of the barrier
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -1366,7 +1418,7 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
         const int64_t jt = slot == CJ_OWN ? ntiles : min<int64_t>(sb->job_tiles, ntiles - j0);
         w0 = uniform64(j0 + jt * wave / NW);
         w1 = uniform64(j0 + jt * (wave + 1) / NW);
-        m = meta_t + (int64_t)(nb + bkt) * ntiles;  // out-run nb + b′ (run-major meta)
+        m = meta_t + (int64_t)(IDX ? bkt : nb + bkt) * ntiles;  // out-run nb + b′ (run-major meta; IDX: run b′)
         pbase = (uint32_t)bkt << C2_BITS;
         ns = (uint32_t)__builtin_amdgcn_readfirstlane((int)*nsp);
         ks0 = ns > 0 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)skb[0]) : 0x10000u;
@@ -1400,16 +1452,18 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
     // self-loops, then the last unit to finish writes the count
     const unsigned long long tot = block_reduce_sum(sum, red);
     unsigned long long l = 0;
-    for (int64_t i = (int64_t)ui * C5_BLOCK + threadIdx.x; i < ntiles; i += (int64_t)nu * C5_BLOCK)
-      l += pr.tile_loops[i];
-    l = block_reduce_sum(l, red);
+    if constexpr (!IDX) {
+      for (int64_t i = (int64_t)ui * C5_BLOCK + threadIdx.x; i < ntiles; i += (int64_t)nu * C5_BLOCK)
+        l += pr.tile_loops[i];
+      l = block_reduce_sum(l, red);
+    }
     if (threadIdx.x == 0) {
       if (tot) atomicAdd(pr.acc3, tot);
       if (l) atomicAdd(pr.acc3 + 1, l);
       __threadfence();
       if (atomicAdd((unsigned int *)(pr.acc3 + 2), 1u) == (unsigned int)nu - 1) {
         __threadfence();
-        const unsigned long long a0 = atomicAdd(pr.acc3, 0ull), a1 = atomicAdd(pr.acc3 + 1, 0ull);
+        const unsigned long long a0 = atomicAdd(pr.acc3, 0ull), a1 = IDX ? *pr.idx_loops : atomicAdd(pr.acc3 + 1, 0ull);
         // fin may be pinned host memory: a system-scope store
         __hip_atomic_store(pr.fin, (int64_t)(a0 - a1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __threadfence_system();
@@ -1453,21 +1507,21 @@ __global__ __launch_bounds__(256) void k_c3_overflow(C3Ovf o, uint32_t *h_in, ui
   }
 }
 
-template <int W, bool ALIAS, bool CHECK, class SH>
+template <int W, bool ALIAS, bool CHECK, class SH, bool ONE = false>
 static void launch_c5(Session *s, const C5Cols<W> &c, uint16_t *part, uint32_t *meta,
                       uint32_t *tile_loops, uint32_t *zbuf, int64_t zwords, unsigned long long *zacc,
                       int run_major = 0) {
-  const int64_t nfull = c.n / SH::TILE;
+  const int64_t nfull = c.n / (ONE ? 2 * SH::TILE : SH::TILE);
   if (nfull > 0) {
     auto kern = c.bu1 == c.lo && c.bv1 == c.lo && W == 3 && !SH::WIDE
-                    ? k_c5_partition<W, ALIAS, CHECK, false, SH, 3>
-                    : k_c5_partition<W, ALIAS, CHECK, false, SH, 2>;
+                    ? k_c5_partition<W, ALIAS, CHECK, false, SH, 3, ONE>
+                    : k_c5_partition<W, ALIAS, CHECK, false, SH, 2, ONE>;
     hipLaunchKernelGGL(kern, dim3((unsigned)nfull), dim3(C5_BLOCK), 0, s->stream, c, part, meta,
                        tile_loops, (int64_t)0, zbuf, zwords, zacc, run_major);
     KERNEL_CHECK();
   }
   if (nfull < c.ntiles) {  // the ragged last tile
-    hipLaunchKernelGGL((k_c5_partition<W, ALIAS, true, true, SH>), dim3(1), dim3(C5_BLOCK), 0,
+    hipLaunchKernelGGL((k_c5_partition<W, ALIAS, true, true, SH, 0, ONE>), dim3(1), dim3(C5_BLOCK), 0,
                        s->stream, c, part, meta, tile_loops, nfull, zbuf, zwords, zacc, run_major);
     KERNEL_CHECK();
   }
@@ -1496,7 +1550,9 @@ struct C5PostLayout {
   int64_t steal_ctl, images;
 };
 
-static C5PostLayout c5_post_layout(int nr, int S, int split_x16, int64_t nkeys, int steal_slots = 0) {
+// images_external: the slots' images live in a buffer of the caller's (a C5InIndex).
+static C5PostLayout c5_post_layout(int nr, int S, int split_x16, int64_t nkeys, int steal_slots = 0,
+                                   bool images_external = false) {
   C5PostLayout l;
   // runs × slices + hub splits (≤ 2 per run beyond the slices), whole XCD waves
   // Σ_runs max(S, ⌈cnt/target⌉) ≤ S·nr + nr + total/target, target ≥ split/16 × mean
@@ -1511,7 +1567,7 @@ static C5PostLayout c5_post_layout(int nr, int S, int split_x16, int64_t nkeys, 
   l.steal_ctl = l.split + 4 * (int64_t)nr;  // nr = 2·nb is even: 8-B aligned like the log
   l.units = l.steal_ctl + 8 * (int64_t)steal_slots;
   l.images = (l.units + (int64_t)sizeof(C3Unit) * l.max_units + 15) & ~int64_t(15);
-  l.bytes = l.images + (int64_t)C5_IMAGE_BYTES * steal_slots;
+  l.bytes = l.images + (images_external ? 0 : (int64_t)C5_IMAGE_BYTES * steal_slots);
   l.zero_bytes = l.units;
   assert(l.log % 8 == 0 && l.units % 8 == 0);  // uint2 entries, C3Unit's int64 fields
   return l;
@@ -1567,6 +1623,7 @@ struct C5PostBufs {
   const uint32_t *tile_loops;
   unsigned long long *acc3;
   int64_t *fin = nullptr;  // mode P: where the last unit writes the count
+  uint4 *images = nullptr;  // mode P: the slots' images when they are not in the work area (an index being built)
 };
 
 // What the dot after c5_post reads: the hand-off log, the split flags (per
@@ -1716,7 +1773,8 @@ static C5PostOut c5_post(Session *s, const C5PostBufs &b, const C5PostPlan &p) {
     assert(!p.probe() || (p.sides.t0[0] == 0 && p.sides.t1[0] == p.ntiles));  // mode P's jobs cut [0, ntiles)
     const C5Probe pr{b.acc3, b.fin, b.tile_loops, p.hotcap,
                      C5Steal{p.steal, p.job_tiles, (uint32_t)l.steal_slots, p.heavy_pieces, (uint32_t *)(nunits + 2),
-                             (uint32_t *)(nunits + 3), sctl, sctl + l.steal_slots, (uint4 *)(base + l.images)}};
+                             (uint32_t *)(nunits + 3), sctl, sctl + l.steal_slots,
+                             b.images ? b.images : (uint4 *)(base + l.images)}};
     auto kern = p.probe() ? k_c5_gather<C5_PPS, true> : k_c5_gather<C5_PPS, false>;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C5_BLOCK), p.probe() ? C5_PROBE_LDS : C5_GATHER_LDS, s->stream,
                        listed ? (const C3Unit *)units : nullptr, (const int32_t *)nunits, b.part,
@@ -1844,26 +1902,183 @@ static void c5_with_flag(bool flag, F &&f) {
   else f(std::false_type{});
 }
 
+// ------------------------------------------------------------- the in-side index
+// The in side of (a)-->(b)-->(c) over ONE rel table is a pure function of the
+// immutable column pair (end(r), start(r)) and the node range: per bucket the
+// 2^16 finished in-degree halves, the special keys (in-degree ≥ 2^16) and, for
+// the table, the self-loop count.  Like the triangle's oriented CSR it is
+// ingest-time work: built by the first query over the pair (which answers
+// through the unindexed mode-P pipeline with every unit publishing its image
+// into this buffer instead of the work area), kept on the end column for the
+// column's lifetime (Column::c5_index), and probed by every later query, which
+// still streams and partitions the whole source column — the count itself is
+// never cached.  34.6 MB at 256 buckets.
+struct C5InIndex {
+  // key: the peer column start(r), the node range and mix, the id width, the rows
+  std::weak_ptr<Column> peer;
+  int64_t lo = 0, len = 0, n = 0;
+  int kbits = 0, width = 0, nb = 0;
+  // nb images (C5_IMAGE_BYTES each, slot s self-describing: its header names its
+  // bucket) | trailer: self-loops (uint64), the build query's hand-off log count (uint32)
+  BufPtr buf;
+  // Pending: the build query is enqueued; whether its units logged (hot table
+  // full — an image is then not self-contained) is read from the trailer, in
+  // stream order, by the next query over the pair
+  enum State { Pending, Ready, Refused } state = Pending;
+  uint4 *images() const { return (uint4 *)buf->p; }
+  unsigned long long *loops() const { return (unsigned long long *)((char *)buf->p + (int64_t)nb * C5_IMAGE_BYTES); }
+  uint32_t *logged() const { return (uint32_t *)(loops() + 1); }
+  bool matches(const C5IndexCols &e, int64_t lo_, int64_t len_, int64_t n_, int kbits_, int width_) const {
+    return peer.lock() == e.start && lo == lo_ && len == len_ && n == n_ && kbits == kbits_ && width == width_;
+  }
+};
+
+// Shapes the index serves: what mode P runs by default on the small P1 shape,
+// with none of the switches set that name a pipeline (their tests keep running
+// the pipelines they name).  CAPF_C5_INDEX=0 turns it off.
+static bool c5_index_enabled() {
+  const char *e = getenv("CAPF_C5_INDEX");
+  if (e && atoi(e) == 0) return false;
+  for (const char *v : {"CAPF_C5_PROBE", "CAPF_C5_DIRECT", "CAPF_P3_SPLIT", "CAPF_C5_STEAL"})
+    if (getenv(v)) return false;
+  return true;
+}
+
+// nb buckets: the small P1 shape, and mode P is what the plan picks by default
+static bool c5_index_shape(int64_t nb) {
+  return 2 * nb + 1 <= C5Small::MAXR && nb >= 256 && c5_slices((int)(2 * nb)) == 1 && c5_index_enabled();
+}
+
+static void c5_count_event(Session *s, const char *name) {
+  auto &e = s->profile[name];
+  e.launches++;
+  e.bytes += 1.0;
+}
+
+// The pair's index if it may answer this query (Ready), after settling a Pending one.
+static std::shared_ptr<C5InIndex> c5_index_lookup(Session *s, const C5IndexCols &e, int64_t lo, int64_t len, int64_t n,
+                                                  int kbits, int width, bool *known) {
+  std::shared_ptr<C5InIndex> ix;
+  {
+    std::lock_guard<std::mutex> lk(e.end->mu);
+    ix = std::static_pointer_cast<C5InIndex>(e.end->c5_index);
+  }
+  *known = ix && ix->matches(e, lo, len, n, kbits, width);
+  if (!*known) return nullptr;
+  if (ix->state == C5InIndex::Pending) {
+    uint32_t logged = 0;
+    HIP_CHECK(hipMemcpyAsync(&logged, ix->logged(), 4, hipMemcpyDeviceToHost, s->stream));
+    s->sync();
+    std::lock_guard<std::mutex> lk(e.end->mu);
+    if (ix->state == C5InIndex::Pending) {
+      ix->state = logged ? C5InIndex::Refused : C5InIndex::Ready;
+      c5_count_event(s, logged ? "c5_index_refused" : "c5_index_builds");
+      if (logged) ix->buf.reset();  // later queries keep the unindexed pipeline
+    }
+  }
+  return ix->state == C5InIndex::Ready ? ix : nullptr;
+}
+
+// A query answered from the index: P1 over the source column only (one key per
+// row, nb out-runs, run-major meta), then the indexed units.  No histogram
+// buffer, no self-loop pass, no memset launch: P1 clears [Σ, loops, done] and
+// the cursors with the work area's zero prefix.
+template <int W, class SH>
+static void chain2_c5_indexed(Session *s, C5Cols<W> c, const C5InIndex &ix, unsigned long long *d_acc3,
+                              C2Spill *spill) {
+  constexpr int ROWS = 2 * SH::TILE;
+  c.ntiles = (c.n + ROWS - 1) / ROWS;
+  const int nr = c.nb;
+  c.rstride = ((int64_t)ROWS + 8 * (nr + 1) + 7) & ~int64_t(7);
+  BufPtr part = s->alloc(2 * c.rstride * c.ntiles);
+  BufPtr meta = s->alloc(4 * (int64_t)nr * c.ntiles);
+  const C5PostLayout l = c5_post_layout(2 * c.nb, 1, 32, c.n, c.nb, true);
+  BufPtr acc = s->alloc(l.bytes);
+  char *base = (char *)acc->p;
+  {
+    KernelTimer kt(s, "c5_partition", (W + 2.0) * c.n);
+    launch_c5<W, true, false, SH, true>(s, c, (uint16_t *)part->p, (uint32_t *)meta->p, nullptr, (uint32_t *)base,
+                                        l.zero_bytes / 4, d_acc3, 1);
+  }
+  static std::once_flag attr_once;
+  std::call_once(attr_once, [] {
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_c5_gather<C5_PPS, true, true>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, C5_PROBE_LDS));
+  });
+  int32_t *counters = (int32_t *)(base + l.counters);
+  uint32_t *sctl = (uint32_t *)(base + l.steal_ctl);
+  const C3Ovf ovf{(uint2 *)(base + l.log), (uint32_t *)(counters + 1), l.ovf_cap};
+  const char *te = getenv("CAPF_C5_STEAL_TILES");
+  const uint32_t job_tiles = (uint32_t)std::max(1, te ? atoi(te) : 512);
+  const C5Probe pr{d_acc3, spill->fin, nullptr, C5_HOT,
+                   C5Steal{C5_STEAL_ALL, job_tiles, (uint32_t)c.nb, 0, (uint32_t *)(counters + 2),
+                           (uint32_t *)(counters + 3), sctl, sctl + c.nb, ix.images()},
+                   ix.loops()};
+  const C3Sides sd{c.nb, {0, 0}, {c.ntiles, c.ntiles}, 32, 0, 0, nullptr};
+  {
+    KernelTimer kt(s, "c5_gather", 2.0 * c.n);
+    hipLaunchKernelGGL((k_c5_gather<C5_PPS, true, true>), dim3((unsigned)((c.nb + 255) / 256 * 256)), dim3(C5_BLOCK),
+                       C5_PROBE_LDS, s->stream, (const C3Unit *)nullptr, (const int32_t *)counters,
+                       (const uint16_t *)part->p, (const uint32_t *)meta->p, c.ntiles, c.nb, c.rstride,
+                       (uint32_t *)nullptr, (uint32_t *)nullptr, (int64_t)0, ovf, sd, 1, (int64_t)1, pr);
+    KERNEL_CHECK();
+  }
+  spill->log = ovf.log;  // (stays empty: diagnostics read its count)
+  spill->n = ovf.n;
+  spill->cap = ovf.cap;
+  spill->steals = ovf.n + 2;  // counters [3]
+  spill->fin_written = true;
+  c5_count_event(s, "c5_index_queries");
+}
+
 // d_acc3 = [Σ in·out, self-loops, done]: P1's tile-0 workgroup clears it, the
 // transpose (or, without one, the dot) adds the self-loops (the caller needs
 // no memset).
+// ends (both hops over one rel table): a Ready index answers the query (h_in /
+// h_out are then not touched); without one, a mode-P query builds it.
 template <int W, class SH>
 static void chain2_c5(Session *s, C5Cols<W> c, bool in_range, uint32_t *h_in, uint32_t *h_out,
-                      unsigned long long *d_acc3, C2Spill *spill) {
+                      unsigned long long *d_acc3, C2Spill *spill, const C5IndexCols *ends, int kbits) {
   c.ntiles = (c.n + SH::TILE - 1) / SH::TILE;
   const int nr = 2 * c.nb;
   c.rstride = ((int64_t)2 * SH::TILE + 8 * (nr + 1) + 7) & ~int64_t(7);
+  C5PostPlan plan = c5_plan_fused(c.nb, c.ntiles, c.rstride, 2 * c.n, spill != nullptr);
+  const bool direct = plan.mode.work == C5Work::Direct;
+  const bool alias = c.u2 == c.u1 && c.v2 == c.v1;
+  // The in-side index: the small shape, ids inside the node range by the column
+  // statistics (the one-sided P1 cannot test a row's target), mode P by default
+  std::shared_ptr<C5InIndex> build;
+  if constexpr (std::is_same<SH, C5Small>::value) {
+    if (ends && spill && alias && in_range && plan.probe() && c5_index_shape(c.nb)) {
+      bool known = false;
+      const std::shared_ptr<C5InIndex> ix = c5_index_lookup(s, *ends, c.lo, (int64_t)c.len, c.n, kbits, W, &known);
+      if (ix) {
+        chain2_c5_indexed<W, SH>(s, c, *ix, d_acc3, spill);
+        return;
+      }
+      if (!known) {  // this query builds it: every unit publishes, into the index's buffer
+        build = std::make_shared<C5InIndex>();
+        build->peer = ends->start;
+        build->lo = c.lo;
+        build->len = (int64_t)c.len;
+        build->n = c.n;
+        build->kbits = kbits;
+        build->width = W;
+        build->nb = c.nb;
+        build->buf = s->alloc((int64_t)c.nb * C5_IMAGE_BYTES + 16);
+        plan.steal = C5_STEAL_ALL;
+        plan.layout = c5_post_layout(nr, plan.S, plan.sides.split_x16, 2 * c.n, c.nb, true);
+      }
+    }
+  }
   BufPtr part = s->alloc(2 * c.rstride * c.ntiles);
   BufPtr meta = s->alloc(4 * nr * c.ntiles);
   BufPtr tl = s->alloc(4 * std::max<int64_t>(c.ntiles, 1));
-  const C5PostPlan plan = c5_plan_fused(c.nb, c.ntiles, c.rstride, 2 * c.n, spill != nullptr);
-  const bool direct = plan.mode.work == C5Work::Direct;
   C5PostBufs bufs{(const uint16_t *)part->p,   (const uint32_t *)meta->p, h_in, h_out,
                   s->alloc(plan.layout.bytes), (const uint32_t *)tl->p,   d_acc3,
-                  spill ? spill->fin : nullptr};
+                  spill ? spill->fin : nullptr, build ? build->images() : nullptr};
   {
     KernelTimer kt(s, "c5_partition", (2.0 * W + 4.0) * c.n);
-    const bool alias = c.u2 == c.u1 && c.v2 == c.v1;
     c5_with_flag(alias, [&](auto al) {
       c5_with_flag(!in_range, [&](auto chk) {
         launch_c5<W, decltype(al)::value, decltype(chk)::value, SH>(
@@ -1895,6 +2110,14 @@ static void chain2_c5(Session *s, C5Cols<W> c, bool in_range, uint32_t *h_in, ui
     spill->cap = out.ovf.cap;
     spill->steals = out.ovf.n + 2;  // counters [3]
     spill->fin_written = true;
+  }
+  if (build) {
+    // the trailer, in stream order behind the units: the self-loop total and the
+    // hand-off log's count (non-zero: some image is not self-contained → refused)
+    HIP_CHECK(hipMemcpyAsync(build->loops(), d_acc3 + 1, 8, hipMemcpyDeviceToDevice, s->stream));
+    HIP_CHECK(hipMemcpyAsync(build->logged(), out.ovf.n, 4, hipMemcpyDeviceToDevice, s->stream));
+    std::lock_guard<std::mutex> lk(ends->end->mu);
+    ends->end->c5_index = build;
   }
   if (plan.S > 1) {
     hipLaunchKernelGGL(k_c5_fold, dim3(grid_for(plan.slice_stride / 4, 256, 1024)), dim3(256), 0, s->stream,
@@ -2434,7 +2657,7 @@ int64_t chain2_hist_len(int64_t len) { return int64_t(1) << chain2_hist_bits(len
 // k_chain2_hist).
 bool chain2_partitioned(Session *s, const ColView *cols, int64_t n, int64_t lo, int64_t hi,
                         bool in_range, uint32_t *h_in, uint32_t *h_out,
-                        unsigned long long *d_acc3, C2Spill *spill) {
+                        unsigned long long *d_acc3, C2Spill *spill, const C5IndexCols *ends) {
   const int64_t len = hi - lo + 1;
   if (len <= 0 || n <= 0) return false;
   const int kbits = chain2_hist_bits(len);
@@ -2450,13 +2673,30 @@ bool chain2_partitioned(Session *s, const ColView *cols, int64_t n, int64_t lo, 
     auto base = [&](int i) { return W != 8 ? cols[i].base : int64_t(0); };
     const C5Cols<W> c{cols[0].data, cols[1].data, cols[2].data, cols[3].data, base(0), base(1), base(2), base(3),
                       n, lo, (uint64_t)len, (int)nb, /* ntiles, rstride: chain2_c5 */ 0, 0, node_mix_for(kbits)};
-    chain2_c5<W, decltype(shape)>(s, c, in_range, h_in, h_out, d_acc3, spill);
+    chain2_c5<W, decltype(shape)>(s, c, in_range, h_in, h_out, d_acc3, spill, ends, kbits);
   };
   auto shaped = [&](auto w) { small ? run(w, C5Small{}) : run(w, C5Big{}); };
   if (width == 3) shaped(std::integral_constant<int, 3>{});
   else if (width == 4) shaped(std::integral_constant<int, 4>{});
   else shaped(std::integral_constant<int, 8>{});
   return true;
+}
+
+// Would chain2_partitioned answer this query from a Ready in-side index?  (The
+// caller then needs no histogram buffer.)  Settles a Pending index like the
+// query itself would.
+bool chain2_index_serves(Session *s, const ColView *cols, int64_t n, int64_t lo, int64_t hi, bool in_range,
+                         const C5IndexCols &ends) {
+  const int64_t len = hi - lo + 1;
+  if (len <= 0 || n <= 0 || n >= (int64_t(1) << 30) || !in_range) return false;
+  if (cols[2].data != cols[0].data || cols[3].data != cols[1].data) return false;
+  const int kbits = chain2_hist_bits(len);
+  if (!c5_index_shape((int64_t(1) << kbits) / C2_BW)) return false;
+  const int64_t rows[4] = {n, n, n, n};
+  const int width = c5_uniform_width(cols, 4, rows);
+  if (!width) return false;
+  bool known = false;
+  return c5_index_lookup(s, ends, lo, len, n, kbits, width, &known) != nullptr;
 }
 
 // ------------------------------------------ partitioned semi-join count

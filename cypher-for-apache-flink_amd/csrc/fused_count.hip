@@ -1358,13 +1358,14 @@ static bool run_chain2(Session *s, const JoinGraph &g, const Chain2 &c, uint64_t
 
   // partitioned histograms are indexed by node_mix(b − lo) over 2^k ≥ len counters
   const int64_t hlen = len > 0 ? std::max(len, chain2_hist_len(len)) : 0;
-  BufPtr h = s->alloc(8 * std::max<int64_t>(hlen, 1) + 64);
+  // (allocated below: a query answered from the in-side index has no histograms)
+  const size_t h_bytes = 8 * std::max<int64_t>(hlen, 1) + 64;
+  BufPtr h;
   BufPtr acc = s->alloc(24);  // Σ in·out, self-loops, the dot's done counter
   bool fin_done = false;  // the dot kernel wrote the async count
   C2Spill spill;          // hand-offs P3 left for the dot (partitioned pipeline)
   bool acc_zeroed = false;  // the partitioned pipeline clears acc itself
-  uint32_t *h1 = (uint32_t *)h->p;
-  uint32_t *h2 = h1 + ((hlen + 15) & ~int64_t(15));  // keep dwordx4 alignment
+  uint32_t *h1 = nullptr, *h2 = nullptr;
   int64_t dot_len = len;
   if (len > 0) {
     Chain2Args a;
@@ -1379,8 +1380,6 @@ static bool run_chain2(Session *s, const JoinGraph &g, const Chain2 &c, uint64_t
     a.wc = wc.map.m;
     a.lo = lo;
     a.hi = hi;
-    a.h1 = h1;
-    a.h2 = h2;
     a.loops = (unsigned long long *)acc->p + 1;
     a.mixed = 0;
     a.mix = node_mix_for(0);
@@ -1391,6 +1390,18 @@ static bool run_chain2(Session *s, const JoinGraph &g, const Chain2 &c, uint64_t
       const ColStats &st = column_stats(s, R.cols[col]);
       in_range = in_range && st.min >= lo && st.max <= hi;
     }
+    // both hops over one rel table: the in side is indexed on end(r) (chain2_partitioned)
+    const bool same_rel = c.u2 == c.u1 && c.v2 == c.v1;
+    const C5IndexCols ends{R.cols[c.v1], R.cols[c.u1]};
+    const bool indexed = n > 0 && want_part && same_rel && chain2_index_serves(s, pc, n, lo, hi, in_range, ends);
+    auto alloc_h = [&](size_t bytes) {
+      h = s->alloc(bytes);
+      h1 = (uint32_t *)h->p;
+      h2 = h1 + ((hlen + 15) & ~int64_t(15));  // keep dwordx4 alignment
+      a.h1 = h1;
+      a.h2 = h2;
+    };
+    if (!indexed) alloc_h(h_bytes);
     tb = host_trace() ? host_us() : 0;
     // the count (Σ − loops) straight into the async slot or the pinned host
     // scalar (no D2H copy; polling that word instead of the stream wait
@@ -1398,13 +1409,15 @@ static bool run_chain2(Session *s, const JoinGraph &g, const Chain2 &c, uint64_t
     int64_t *fin = s->async_out ? s->async_out : s->h_scalars;
     spill.fin = fin;
     if (n > 0 && want_part &&
-        chain2_partitioned(s, pc, n, lo, hi, in_range, h1, h2, (unsigned long long *)acc->p, &spill)) {
+        chain2_partitioned(s, pc, n, lo, hi, in_range, h1, h2, (unsigned long long *)acc->p, &spill,
+                           same_rel ? &ends : nullptr)) {
       dot_len = chain2_hist_len(len);  // every counter written; loops accumulated on the device
       acc_zeroed = true;
     } else {
+      if (!h) alloc_h(h_bytes);
       HIP_CHECK(hipMemsetAsync(acc->p, 0, 24, s->stream));
       acc_zeroed = true;
-      HIP_CHECK(hipMemsetAsync(h->p, 0, 8 * std::max<int64_t>(hlen, 1) + 64, s->stream));
+      HIP_CHECK(hipMemsetAsync(h->p, 0, h_bytes, s->stream));
       if (n > 0) {
         KernelTimer kt(s, "chain2_hist", 16.0 * n);
         unsigned grid = grid_for(n, 256, 256 * 32);

@@ -34,14 +34,20 @@ tot = 0.0
 # the triangle's STATS=true count kernels run only in a profiled query's untimed
 # diagnostics launch (probe / hit counters), not in a query: listed, not summed
 diag = lambda k: k.startswith("k_tri_count_") and ", true," in k  # noqa: E731
+# a kernel dispatched once while others ran in every query is the first query's
+# build work (the 2-hop count's in-side index is stored by the unindexed
+# pipeline of the first query over a rel table): listed, not summed
+most = max((len(v) for v in list(fetch.values()) + list(write.values())), default=0)
+first = lambda k: not prefix and most > 2 and len(fetch.get(k, write.get(k, []))) == 1  # noqa: E731
 for k in sorted(set(fetch) | set(write)):
     f = fetch.get(k, [0.0])
     w = write.get(k, [0.0])
     fb = 2.0 * sum(f) / len(f)  # corrected read bytes per dispatch
     wb = sum(w) / len(w)
-    (res.setdefault("diagnostics", {}) if diag(k) else res["kernels"])[k] = {
-        "dispatches": len(f), "read_bytes": fb, "write_bytes": wb, "fetch_size_raw_bytes": sum(f) / len(f)}
-    if not diag(k):
+    where = res.setdefault("diagnostics", {}) if diag(k) else res.setdefault("first_query", {}) if first(k) \
+        else res["kernels"]
+    where[k] = {"dispatches": len(f), "read_bytes": fb, "write_bytes": wb, "fetch_size_raw_bytes": sum(f) / len(f)}
+    if where is res["kernels"]:
         tot += fb + wb
 res["hbm_bytes_per_query"] = tot
 lib = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cypher-for-apache-flink_amd",
