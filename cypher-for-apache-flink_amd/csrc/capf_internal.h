@@ -761,6 +761,8 @@ struct C2Spill {
   bool fin_written = false;
   // probe mode: jobs of a bucket's out-run run by a unit other than its owner (diagnostics)
   const uint32_t *steals = nullptr;
+  // probe mode: jobs of phase 2 run by all units (diagnostics)
+  const uint32_t *jobs = nullptr;
 };
 // d_acc3 = [Σ in·out, self-loops, done counter] (device): the pipeline writes
 // the self-loop total into [1] and clears [0] and [2] itself (no memset needed)

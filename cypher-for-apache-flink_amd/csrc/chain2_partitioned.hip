@@ -647,9 +647,13 @@ constexpr uint32_t C5_HOT_EMPTY = 0xFFFFFFFFu;
 // Mode P, phase 2 shared between units.  A unit that publishes copies what
 // phase 2 reads of its bucket (the image: 2^16 halves, bucket id, special keys
 // and their extras) into a slot of the work area and hands its out-run out as
-// jobs of job_tiles tiles from the slot's cursor; a unit that has finished its
-// own bucket loads a ready slot's image into its LDS and takes jobs from that
-// cursor.  Nobody waits: a slot that is not ready yet is passed over.
+// jobs, tile ranges drawn from the slot's cursor (which counts tiles: a taker
+// adds the length it claims); a unit that has finished its own bucket loads a
+// ready slot's image into its LDS and takes jobs from that cursor.  Nobody
+// waits: a slot that is not ready yet is passed over.  Mode P's jobs are
+// job_tiles long.  An indexed unit (IDX) sizes the jobs of its slot by work:
+// it sums the pieces of the slot's out-run and leaves in jobt[slot] the length
+// that cuts the run into round(pieces / job_pieces) equal ranges.
 enum : uint32_t {
   C5_STEAL_OFF = 0,
   C5_STEAL_HEAVY = 1,  // units whose in-run or out-run exceeds heavy_pieces publish
@@ -663,13 +667,16 @@ constexpr int C5_HEAVY_SLOTS = 16;
 // walks, and as kernel arguments they would sit in SGPRs across the walks.
 struct C5Steal {
   uint32_t steal;         // C5_STEAL_*
-  uint32_t job_tiles;     // tiles of an out-run per job
+  uint32_t job_tiles;     // tiles of an out-run per job (IDX: at least; and of a slot whose jobt[] is still 0)
   uint32_t nslots;        // image slots
   uint32_t heavy_pieces;  // C5_STEAL_HEAVY: a unit publishes when a run of its holds more pieces
+  uint32_t job_pieces;    // IDX: pieces of an out-run per job (0: every job is job_tiles long, jobt[] stays 0)
   uint32_t *slots_used;   // slots claimed so far (may pass nslots: the late claimers do not publish)
   uint32_t *steals;       // jobs run by a unit other than the bucket's owner (profile)
+  uint32_t *jobs;         // jobs run (profile)
   uint32_t *ready;        // [nslots] the slot's image is complete
-  uint32_t *cursor;       // [nslots] next job of the slot's out-run
+  uint32_t *cursor;       // [nslots] next tile of the slot's out-run
+  uint32_t *jobt;         // [nslots] IDX: tiles per job of the slot, 0 until its unit has set it
   uint4 *images;          // [nslots] × C5_IMAGE_BYTES
 };
 
@@ -683,7 +690,8 @@ struct C5Probe {
 };
 
 // the unit's job mailbox in LDS (words)
-enum { CJ_SLOT, CJ_IDX, CJ_NEED, CJ_CUR, CJ_IMG, CJ_NSTEAL, CJ_BKT, CJ_PIN, CJ_POUT, CJ_MINE, CJ_WORDS = 12 };
+// (CJ_T0, CJ_LEN: the job's tiles; CJ_NJOBS, CJ_NSTEAL: the unit's jobs so far, those of other units' buckets)
+enum { CJ_SLOT, CJ_T0, CJ_NEED, CJ_CUR, CJ_IMG, CJ_NSTEAL, CJ_BKT, CJ_PIN, CJ_POUT, CJ_MINE, CJ_LEN, CJ_NJOBS, CJ_WORDS = 12 };
 constexpr int CJ_NONE = -1, CJ_OWN = -2, CJ_OWN_PENDING = -3;
 
 __device__ inline void c5_log_append(uint2 *log, uint32_t *n, uint32_t cap, uint32_t gkey, uint32_t count) {
@@ -1128,6 +1136,27 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
         job[CJ_MINE] = ui;
         job[CJ_BKT] = ui;
       }
+      // The weight of slot ui's out-run (its bucket is named by the image's
+      // header): one pass over the run's 4·ntiles B of meta, as the heavy
+      // publishers of mode P make.  The run is cut into k = round(T / job_pieces)
+      // ranges of ⌈ntiles / k⌉ tiles (work per tile is taken as uniform within a
+      // run), not shorter than job_tiles.  T = 0: one job that walks nothing.
+      // Everything stays in the mailbox: no register lives across the walks.
+      if (st->job_pieces) {
+        const uint32_t bk = ((const uint32_t *)(st->images + (int64_t)ui * (C5_IMAGE_BYTES / 16) + 2 * C2_BW / 16))[1];
+        const uint32_t *mo = meta_t + (int64_t)bk * ntiles;
+        uint32_t q = 0;
+        for (int64_t t = threadIdx.x; t < ntiles; t += C5_BLOCK) q += ((mo[t] >> 16) + 7) >> 3;
+        q = (uint32_t)wave_reduce_sum((unsigned long long)q);
+        if (lane == 0 && q) atomicAdd(&job[CJ_POUT], (int)q);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+          const uint32_t T = (uint32_t)job[CJ_POUT], W = st->job_pieces, nt = (uint32_t)ntiles;
+          const uint32_t k = max(1u, (uint32_t)(((unsigned long long)T + W / 2) / W));
+          const uint32_t jt = min(nt, max(st->job_tiles, (nt + k - 1) / k));
+          __hip_atomic_store(&st->jobt[ui], jt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
     } else {
     __syncthreads();
     // Finalise: every half is < 2^15 now and nothing adds any more, so a half
@@ -1329,6 +1358,15 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
     // load per slot; a slot that is not ready is passed over — no unit waits
     // for another, and every cursor add that fails retires its slot for good,
     // so the search ends).
+    // A slot's cursor counts tiles.  A taker picks a length jl (mode P: job_tiles;
+    // IDX: jobt[slot], or job_tiles while that is still 0) and adds it: the add
+    // returns a start c no other add returns and moves the cursor by exactly
+    // the jl it claims, so the ranges [c, min(c + jl, ntiles)) of the adds with
+    // c < ntiles are disjoint and cover [0, ntiles) whatever jl each taker used;
+    // an add with c ≥ ntiles has failed.  jobt[] therefore needs no ordering
+    // (relaxed store, relaxed loads): any value read gives a correct partition,
+    // the word only steers the jobs' sizes.  (A slot sees at most one failed
+    // add per unit, each ≤ ntiles: the cursor stays below 2^32.)
     for (;;) {
       // (laundered offset: the addresses of the mailbox, the parked arguments and
       // the specials are loop invariants, one SGPR each if hoisted out of the job
@@ -1339,18 +1377,29 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
       const C5Steal *const sb = (const C5Steal *)(jb + CJ_WORDS);
       uint32_t *const nsp = nspec + z, *const skb = sk + z, *const sxb = sx + z;
       if (wave == 0) {
-        const uint32_t jtl = (uint32_t)__builtin_amdgcn_readfirstlane((int)sb->job_tiles);
-        const uint32_t njobs = sb->steal ? ((uint32_t)ntiles + jtl - 1) / jtl : 0u;
+        const uint32_t nt = (uint32_t)ntiles;
+        // lane 0 draws a job from slot sl's cursor: its first tile (≥ nt: none left) and its length
+        auto draw = [&](uint32_t sl, uint32_t *len) -> uint32_t {
+          uint32_t jl = sb->job_tiles, c = 0;
+          if (lane == 0) {
+            if constexpr (IDX) {
+              const uint32_t w = __hip_atomic_load(&sb->jobt[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              jl = w ? w : jl;
+            }
+            c = atomicAdd(&sb->cursor[sl], jl);
+          }
+          *len = (uint32_t)__builtin_amdgcn_readfirstlane((int)jl);
+          return (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
+        };
         int found = CJ_NONE;
-        uint32_t ji = 0;
+        uint32_t jt0 = 0, jlen = nt;  // the unit's own static job: every tile
         const int cur = jb[CJ_CUR];
         if (cur == CJ_OWN_PENDING) {
           found = CJ_OWN;
         } else if (sb->steal) {
           if (cur >= 0) {
-            uint32_t c = lane == 0 ? atomicAdd(&sb->cursor[cur], 1u) : 0u;
-            c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-            if (c < njobs) found = cur, ji = c;
+            const uint32_t c = draw((uint32_t)cur, &jlen);
+            if (c < nt) found = cur, jt0 = c;
           }
           if (found < 0) {
             const uint32_t nsl =
@@ -1361,14 +1410,13 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
               bool cand = sl < nsl;
               if (!IDX && cand)
                 cand = __hip_atomic_load(&sb->ready[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-              if (cand) cand = __hip_atomic_load(&sb->cursor[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < njobs;
+              if (cand) cand = __hip_atomic_load(&sb->cursor[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nt;
               unsigned long long mask = __builtin_amdgcn_ballot_w64(cand);
               while (mask && found < 0) {
                 const uint32_t sc = s0 + (uint32_t)__builtin_ctzll(mask);
                 mask &= mask - 1;
-                uint32_t c = lane == 0 ? atomicAdd(&sb->cursor[sc], 1u) : 0u;
-                c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-                if (c < njobs) found = (int)sc, ji = c;
+                const uint32_t c = draw(sc, &jlen);
+                if (c < nt) found = (int)sc, jt0 = c;
               }
             }
           }
@@ -1380,10 +1428,12 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
         }
         if (lane == 0) {
           jb[CJ_SLOT] = found;
-          jb[CJ_IDX] = (int)ji;
+          jb[CJ_T0] = (int)jt0;
+          jb[CJ_LEN] = (int)min(jlen, nt - jt0);
           jb[CJ_NEED] = need;
           jb[CJ_CUR] = found >= 0 ? found : CJ_NONE;
           if (need) jb[CJ_IMG] = found;
+          if (found != CJ_NONE) jb[CJ_NJOBS] += 1;
           if (found >= 0 && found != jb[CJ_MINE]) jb[CJ_NSTEAL] += 1;
         }
       }
@@ -1414,8 +1464,7 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
       {
         const int bkt = __builtin_amdgcn_readfirstlane(jb[CJ_BKT]);
         // (mode P: every run's tiles are [0, ntiles))
-        const int64_t j0 = slot == CJ_OWN ? 0 : (int64_t)jb[CJ_IDX] * sb->job_tiles;
-        const int64_t jt = slot == CJ_OWN ? ntiles : min<int64_t>(sb->job_tiles, ntiles - j0);
+        const int64_t j0 = jb[CJ_T0], jt = jb[CJ_LEN];
         w0 = uniform64(j0 + jt * wave / NW);
         w1 = uniform64(j0 + jt * (wave + 1) / NW);
         m = meta_t + (int64_t)(IDX ? bkt : nb + bkt) * ntiles;  // out-run nb + b′ (run-major meta; IDX: run b′)
@@ -1448,6 +1497,7 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
       }
     }
     if (threadIdx.x == 0 && job[CJ_NSTEAL]) atomicAdd(st->steals, (uint32_t)job[CJ_NSTEAL]);
+    if (threadIdx.x == 0 && job[CJ_NJOBS]) atomicAdd(st->jobs, (uint32_t)job[CJ_NJOBS]);
     // Epilogue (as k_chain2_dot_pairs): Σ and this unit's share of the
     // self-loops, then the last unit to finish writes the count
     const unsigned long long tot = block_reduce_sum(sum, red);
@@ -1532,9 +1582,10 @@ static void launch_c5(Session *s, const C5Cols<W> &c, uint16_t *part, uint32_t *
 // totals, the work list,) P3 and (the overflow hand-offs).  What it launches is
 // a C5PostPlan, built by c5_plan_fused or c5_plan_sharded and by nothing else.
 
-// Work area of the post-P1 kernels: run_total[nr] (uint64) | counters (4 ×
-// int32: [0] units, [1] hand-off events, [2] image slots claimed, [3] steals) |
-// hand-off log | split[nr] | ready[slots], cursor[slots] | units | images.
+// Work area of the post-P1 kernels: run_total[nr] (uint64) | counters (8 ×
+// int32: [0] units, [1] hand-off events, [2] image slots claimed, [3] steals,
+// [4] jobs) | hand-off log | split[nr] | ready[slots], cursor[slots],
+// jobt[slots] | units | images.
 // Byte offsets; the first `zero_bytes` must start at zero — the run totals and
 // counters are added to, a reserved log slot may be read before its owner
 // wrote it (a zero entry adds nothing), and the split flags are read by the
@@ -1543,9 +1594,9 @@ struct C5PostLayout {
   int max_units;     // capacity of the work list (whole XCD waves)
   uint32_t ovf_cap;  // capacity of the hand-off log
   int64_t run_total, counters, log, split, units, bytes, zero_bytes;
-  // mode P with work sharing: counters [2] slots claimed, [3] steals; the slots'
-  // ready flags and job cursors (zeroed) in front of the units; the images (never
-  // cleared: a slot is read only behind its ready flag) at the end
+  // mode P with work sharing: counters [2] slots claimed, [3] steals, [4] jobs; the
+  // slots' ready flags, tile cursors and job lengths (zeroed) in front of the units;
+  // the images (never cleared: a slot is read only behind its ready flag) at the end
   int steal_slots;
   int64_t steal_ctl, images;
 };
@@ -1561,11 +1612,11 @@ static C5PostLayout c5_post_layout(int nr, int S, int split_x16, int64_t nkeys, 
   l.ovf_cap = (uint32_t)(nkeys / (1 << 15) + 64 + 16 * (int64_t)l.max_units);
   l.run_total = 0;
   l.counters = l.run_total + 8 * (int64_t)nr;
-  l.log = l.counters + 16;
+  l.log = l.counters + 32;
   l.split = l.log + 8 * (int64_t)l.ovf_cap;
   l.steal_slots = steal_slots;
   l.steal_ctl = l.split + 4 * (int64_t)nr;  // nr = 2·nb is even: 8-B aligned like the log
-  l.units = l.steal_ctl + 8 * (int64_t)steal_slots;
+  l.units = (l.steal_ctl + 12 * (int64_t)steal_slots + 7) & ~int64_t(7);
   l.images = (l.units + (int64_t)sizeof(C3Unit) * l.max_units + 15) & ~int64_t(15);
   l.bytes = l.images + (images_external ? 0 : (int64_t)C5_IMAGE_BYTES * steal_slots);
   l.zero_bytes = l.units;
@@ -1610,6 +1661,39 @@ struct C5PostPlan {
   uint32_t steal = C5_STEAL_OFF, job_tiles = 0, heavy_pieces = 0;
   bool probe() const { return mode.counters == C5Counters::Probed; }
 };
+
+// The knobs of the shared phase 2, read per query.
+struct C5StealKnobs {
+  uint32_t steal;      // CAPF_C5_STEAL: 0 = off (every unit probes its own out-run and nothing else), all =
+                       // every unit publishes, reload (tests) = every unit publishes and re-reads its own
+                       // image; unset (or another number) = heavy units publish
+  double theta;        // CAPF_C5_STEAL_THETA: heavy = more than (1 + theta) × the mean pieces in a run
+  uint32_t tiles;      // CAPF_C5_STEAL_TILES: tiles per job (mode P); the shortest job (indexed units); 0 = unset
+  uint32_t job_split;  // CAPF_C5_JOB_SPLIT: indexed units cut a mean out-run into this many jobs (0: jobs of `tiles`)
+};
+constexpr uint32_t C5_JOB_TILES = 512;     // mode P
+constexpr uint32_t C5_IDX_MIN_TILES = 32;  // indexed units (profiles/index_jobs_sweep.txt)
+constexpr uint32_t C5_IDX_JOB_SPLIT = 4;
+
+static C5StealKnobs c5_steal_knobs() {
+  const char *se = getenv("CAPF_C5_STEAL"), *te = getenv("CAPF_C5_STEAL_TILES"), *th = getenv("CAPF_C5_STEAL_THETA");
+  const char *js = getenv("CAPF_C5_JOB_SPLIT");
+  C5StealKnobs k;
+  k.steal = !se                    ? C5_STEAL_HEAVY
+            : !strcmp(se, "all")    ? C5_STEAL_ALL
+            : !strcmp(se, "reload") ? C5_STEAL_RELOAD
+            : atoi(se) != 0         ? C5_STEAL_HEAVY
+                                    : C5_STEAL_OFF;
+  k.theta = th ? atof(th) : 0.15;
+  k.tiles = te ? (uint32_t)std::max(1, atoi(te)) : 0u;
+  k.job_split = js ? (uint32_t)std::max(0, atoi(js)) : C5_IDX_JOB_SPLIT;
+  return k;
+}
+
+// Mean pieces of a run of nkeys / nb keys over ntiles tiles (keys + ~3.5 pad keys per tile, in eights).
+static double c5_mean_pieces(double nkeys, int nb, int64_t ntiles) {
+  return (nkeys / nb + 3.5 * (double)ntiles) / 8;
+}
 
 // part / meta: P1's ntiles tiles of nr = 2·nb runs.  Histograms: S slices per
 // side, slice k at h_in / h_out + k·slice_stride; every counter of every slice
@@ -1681,22 +1765,15 @@ static C5PostPlan c5_plan_fused(int nb, int64_t ntiles, int64_t rstride, int64_t
   const char *hc = getenv("CAPF_C5_HOTCAP");
   if (hc) p.hotcap = (uint32_t)std::min(C5_HOT, std::max(1, atoi(hc)));
   if (p.probe()) {
-    // Phase 2 shared between units, on wherever mode P is.  CAPF_C5_STEAL: 0 =
-    // off (every unit probes its own out-run and nothing else), all = every
-    // unit publishes, reload (tests) = every unit publishes and re-reads its
-    // own image; unset = heavy units publish: those holding more than
-    // (1 + CAPF_C5_STEAL_THETA) × the mean pieces (keys + ~3.5 pad keys per tile,
-    // in eights) in their in-run or out-run.  CAPF_C5_STEAL_TILES: tiles per job.
-    const char *se = getenv("CAPF_C5_STEAL"), *te = getenv("CAPF_C5_STEAL_TILES"), *th = getenv("CAPF_C5_STEAL_THETA");
-    p.steal = !se                    ? C5_STEAL_HEAVY
-              : !strcmp(se, "all")    ? C5_STEAL_ALL
-              : !strcmp(se, "reload") ? C5_STEAL_RELOAD
-              : atoi(se) != 0         ? C5_STEAL_HEAVY
-                                      : C5_STEAL_OFF;
-    p.job_tiles = (uint32_t)std::max(1, te ? atoi(te) : 512);
-    const double mean = ((double)nkeys / 2 / nb + 3.5 * (double)ntiles) / 8;
+    // Phase 2 shared between units, on wherever mode P is (C5StealKnobs).  By
+    // default the heavy units publish: those holding more than (1 + theta) × the
+    // mean pieces in their in-run or out-run.
+    const C5StealKnobs k = c5_steal_knobs();
+    p.steal = k.steal;
+    p.job_tiles = k.tiles ? k.tiles : C5_JOB_TILES;
     // (floor: a run of under 2^16 keys is probed in less time than its image takes to publish)
-    p.heavy_pieces = (uint32_t)std::min(4.0e9, std::max(8192.0, (1.0 + (th ? atof(th) : 0.15)) * mean));
+    p.heavy_pieces =
+        (uint32_t)std::min(4.0e9, std::max(8192.0, (1.0 + k.theta) * c5_mean_pieces((double)nkeys / 2, nb, ntiles)));
     const int slots = p.steal == C5_STEAL_OFF ? 0 : p.steal == C5_STEAL_HEAVY ? C5_HEAVY_SLOTS : nb;
     p.layout = c5_post_layout(2 * nb, p.S, p.sides.split_x16, nkeys, slots);
   }
@@ -1772,9 +1849,9 @@ static C5PostOut c5_post(Session *s, const C5PostBufs &b, const C5PostPlan &p) {
     uint32_t *sctl = (uint32_t *)(base + l.steal_ctl);
     assert(!p.probe() || (p.sides.t0[0] == 0 && p.sides.t1[0] == p.ntiles));  // mode P's jobs cut [0, ntiles)
     const C5Probe pr{b.acc3, b.fin, b.tile_loops, p.hotcap,
-                     C5Steal{p.steal, p.job_tiles, (uint32_t)l.steal_slots, p.heavy_pieces, (uint32_t *)(nunits + 2),
-                             (uint32_t *)(nunits + 3), sctl, sctl + l.steal_slots,
-                             b.images ? b.images : (uint4 *)(base + l.images)}};
+                     C5Steal{p.steal, p.job_tiles, (uint32_t)l.steal_slots, p.heavy_pieces, 0u, (uint32_t *)(nunits + 2),
+                             (uint32_t *)(nunits + 3), (uint32_t *)(nunits + 4), sctl, sctl + l.steal_slots,
+                             sctl + 2 * l.steal_slots, b.images ? b.images : (uint4 *)(base + l.images)}};
     auto kern = p.probe() ? k_c5_gather<C5_PPS, true> : k_c5_gather<C5_PPS, false>;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C5_BLOCK), p.probe() ? C5_PROBE_LDS : C5_GATHER_LDS, s->stream,
                        listed ? (const C3Unit *)units : nullptr, (const int32_t *)nunits, b.part,
@@ -2008,11 +2085,16 @@ static void chain2_c5_indexed(Session *s, C5Cols<W> c, const C5InIndex &ix, unsi
   int32_t *counters = (int32_t *)(base + l.counters);
   uint32_t *sctl = (uint32_t *)(base + l.steal_ctl);
   const C3Ovf ovf{(uint2 *)(base + l.log), (uint32_t *)(counters + 1), l.ovf_cap};
-  const char *te = getenv("CAPF_C5_STEAL_TILES");
-  const uint32_t job_tiles = (uint32_t)std::max(1, te ? atoi(te) : 512);
+  // Jobs of equal work: a mean out-run is cut into job_split jobs, a run of x times
+  // the mean into ~x · job_split, none shorter than min_tiles (C5Steal::job_pieces).
+  const C5StealKnobs k = c5_steal_knobs();
+  const uint32_t min_tiles = k.tiles ? k.tiles : C5_IDX_MIN_TILES;
+  const uint32_t job_pieces =
+      k.job_split ? (uint32_t)std::max(1.0, c5_mean_pieces((double)c.n, c.nb, c.ntiles) / k.job_split) : 0u;
   const C5Probe pr{d_acc3, spill->fin, nullptr, C5_HOT,
-                   C5Steal{C5_STEAL_ALL, job_tiles, (uint32_t)c.nb, 0, (uint32_t *)(counters + 2),
-                           (uint32_t *)(counters + 3), sctl, sctl + c.nb, ix.images()},
+                   C5Steal{C5_STEAL_ALL, min_tiles, (uint32_t)c.nb, 0, job_pieces, (uint32_t *)(counters + 2),
+                           (uint32_t *)(counters + 3), (uint32_t *)(counters + 4), sctl, sctl + c.nb, sctl + 2 * c.nb,
+                           ix.images()},
                    ix.loops()};
   const C3Sides sd{c.nb, {0, 0}, {c.ntiles, c.ntiles}, 32, 0, 0, nullptr};
   {
@@ -2027,6 +2109,7 @@ static void chain2_c5_indexed(Session *s, C5Cols<W> c, const C5InIndex &ix, unsi
   spill->n = ovf.n;
   spill->cap = ovf.cap;
   spill->steals = ovf.n + 2;  // counters [3]
+  spill->jobs = ovf.n + 3;    // counters [4]
   spill->fin_written = true;
   c5_count_event(s, "c5_index_queries");
 }
@@ -2109,6 +2192,7 @@ static void chain2_c5(Session *s, C5Cols<W> c, bool in_range, uint32_t *h_in, ui
     spill->n = out.ovf.n;
     spill->cap = out.ovf.cap;
     spill->steals = out.ovf.n + 2;  // counters [3]
+    spill->jobs = out.ovf.n + 3;    // counters [4]
     spill->fin_written = true;
   }
   if (build) {

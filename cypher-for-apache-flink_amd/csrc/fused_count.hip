@@ -1461,12 +1461,14 @@ static bool run_chain2(Session *s, const JoinGraph &g, const Chain2 &c, uint64_t
     return true;
   }
   if (s->profiling && spill.n) {  // diagnostics (profiling mode only): hand-off log entries
-    uint32_t ne = 0, nst = 0;
+    uint32_t ne = 0, nst = 0, nj = 0;
     HIP_CHECK(hipMemcpyAsync(&ne, spill.n, 4, hipMemcpyDeviceToHost, s->stream));
     if (spill.steals) HIP_CHECK(hipMemcpyAsync(&nst, spill.steals, 4, hipMemcpyDeviceToHost, s->stream));
+    if (spill.jobs) HIP_CHECK(hipMemcpyAsync(&nj, spill.jobs, 4, hipMemcpyDeviceToHost, s->stream));
     s->sync();
     s->profile["c3_handoffs"].bytes += (double)ne;
     if (spill.steals) s->profile["c5_steals"].bytes += (double)nst;
+    if (spill.jobs) s->profile["c5_jobs"].bytes += (double)nj;
   }
   if (fin_done) {
     s->sync();
