@@ -184,6 +184,7 @@ _SIGS = {
     "capf_table_name_list": (c_int32, [_T, c_int32, _STRS, POINTER(c_int32), POINTER(c_int64), c_char_p, _PT]),
     "capf_table_list_columns": (c_int32, [_T, c_int32, _STRS, c_char_p, _PT]),
     "capf_table_list_fn": (c_int32, [_T, c_int32, c_int32, _STRS, c_char_p, _PT]),
+    "capf_table_str_split": (c_int32, [_T, c_char_p, c_char_p, c_char_p, _PT]),
     "capf_table_list_lambda": (c_int32, [_T, c_int32, c_char_p, POINTER(CapfExpr), POINTER(CapfExpr), c_char_p, c_int32, c_char_p, _PT]),
     "capf_session_value_map": (c_int32, [_S, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_int64,
                                          POINTER(c_int32)]),

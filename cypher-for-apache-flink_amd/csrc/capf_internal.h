@@ -277,7 +277,7 @@ __device__ inline bool ft_load(const FtOperand &o, int64_t r, int64_t &val) {
 // ------------------------------------------------------------- plan nodes
 enum class Kind {
   Source, Select, Filter, Join, Union, Distinct, Group, WithColumns, OrderBy, Skip, Limit, Explode, NameList,
-  ListColumns, ListFn, ListLambda
+  ListColumns, ListFn, ListLambda, StrSplit
 };
 
 struct AggSpec {
@@ -333,6 +333,7 @@ struct Node {
   // body (empty code: absent); list_elem = the element / result type, and
   // lambda_types the types of the lambda slots the programs were checked with
   std::vector<Type> lambda_types;
+  // StrSplit (capf_table_str_split): name_cols = (subject, delimiter), list_elem = STRING
 
   // memoised result
   std::mutex mu;
@@ -667,6 +668,9 @@ void string_heap_append(Session *s, size_t n0, int64_t base, const int64_t *d_of
 // −2 "evaluate on the host".
 void string_fn_codes(Session *s, int32_t fn, int64_t iarg0, int64_t iarg1, int64_t lit0, int64_t lit1,
                      const int64_t *src, int64_t c0, int64_t n, int64_t *out);
+// split(subject, delimiter) per row of d (capf_table_str_split, string_fn.hip):
+// a LIST<STRING> column, its pieces interned on the device; both columns STRING.
+ColPtr str_split_column(Session *s, const Data &d, int subject_col, int delim_col);
 // Record an error for capf_last_error() (used by entry points outside runtime.cpp).
 int32_t record_error(int32_t code, const char *msg);
 

@@ -713,6 +713,16 @@ static DataPtr materialize_impl(const NodePtr &n) {
                               : list_fn_column(s, *c, n->list_fn, n->name_cols, n->list_elem));
       return out;
     }
+    case Kind::StrSplit: {
+      DataPtr c = materialize(n->kids[0]);
+      auto out = std::make_shared<Data>();
+      out->nrows = c->nrows;
+      out->cols = c->cols;
+      out->cols.push_back(n->types.back() == Type::Null
+                              ? null_column(s, Type::Null, c->nrows)
+                              : str_split_column(s, *c, n->name_cols[0], n->name_cols[1]));
+      return out;
+    }
     case Kind::ListLambda: {
       DataPtr c = materialize(n->kids[0]);
       auto out = std::make_shared<Data>();
@@ -2008,6 +2018,7 @@ static bool static_list_elem(const NodePtr &n, int i, Type &et, int depth = 0) {
     case Kind::ListColumns:
     case Kind::ListFn:
     case Kind::ListLambda:
+    case Kind::StrSplit:
       if (i < nk) return static_list_elem(n->kids[0], i, et, depth + 1);
       et = n->list_elem;
       return true;
@@ -2661,6 +2672,34 @@ capf_status capf_table_list_fn(capf_table *t, int32_t fn, int32_t nargs, const c
       integer_arg(2, "a slice bound");
     }
   }
+  nn->names.emplace_back(name);
+  nn->types.push_back(out_type);
+  *out = wrap(nn);
+  CAPF_API_END
+}
+
+capf_status capf_table_str_split(capf_table *t, const char *str_col, const char *delim_col, const char *name,
+                                 capf_table **out) {
+  CAPF_API_BEGIN
+  need(t, "table");
+  need(str_col, "str_col");
+  need(delim_col, "delim_col");
+  need(name, "name");
+  need(out, "out");
+  const NodePtr &c = t->node;
+  if (c->col_index(name) >= 0) illegal(std::string("column '") + name + "' already exists");
+  auto nn = new_node(c->s, Kind::StrSplit);
+  nn->kids.push_back(c);
+  nn->names = c->names;
+  nn->types = c->types;
+  nn->name_cols = {c->col_index_or_throw(str_col), c->col_index_or_throw(delim_col)};
+  Type out_type = Type::List;
+  for (int j : nn->name_cols) {
+    const Type ct = c->types[(size_t)j];
+    if (ct == Type::Null) out_type = Type::Null;  // a NULL operand: a NULL list
+    else if (ct != Type::String) illegal(std::string("split() of a ") + type_name(ct) + " column, not a STRING");
+  }
+  nn->list_elem = Type::String;
   nn->names.emplace_back(name);
   nn->types.push_back(out_type);
   *out = wrap(nn);

@@ -29,6 +29,9 @@
 // representative with an atomicMin of its position, and a prefix sum over the
 // representatives ranks them: new codes ascend in the order of the smallest
 // position producing each string, whatever the order the threads ran in.
+// The interning is one function (intern_results) with two callers: the string
+// functions above and split(subject, delimiter) per table row
+// (capf_table_str_split), whose kernels and byte formulas are at the end.
 #include <algorithm>
 #include <cstring>
 
@@ -566,6 +569,109 @@ static int64_t read_counter(Session *s, const BufPtr &cnt) {
   return s->h_scalars[0];
 }
 
+// ------------------------------------------------------------ interning
+// The n results of a device step — statuses st, the bytes rbytes[roff[i],
+// roff[i + 1]) of a scratch heap of `total` bytes — interned against the n0
+// strings of the heap snapshot h (index_mu held).  Returns the device codes:
+// −1 NULL, −2 host, the source's code (dsrc / c0) for an identity, else the
+// code of the result's bytes.  New strings are appended to the heap and the
+// dictionary, their codes ascending by the smallest position producing each.
+// `out` non-null: the codes go to the host too, in the step's one
+// synchronisation; null: they stay on the device (split's element column).
+static BufPtr intern_results(Session *s, const StringHeap &h, size_t n0, const int64_t *dsrc, int64_t c0, int64_t n,
+                             const BufPtr &st, const BufPtr &roff, const BufPtr &rbytes, int64_t total,
+                             int64_t *out) {
+  const int64_t *off = (const int64_t *)h.off->p;
+  const uint8_t *bytes = (const uint8_t *)h.bytes->p;
+  const dim3 grid(grid_for(n, SF_BLOCK)), block(SF_BLOCK);
+  ensure_index(s, h, n0);
+  const Session::StrIndex &ix = s->str_index;
+  BufPtr rhash = s->alloc(8 * (size_t)n), d_out = s->alloc(8 * (size_t)n), grp = s->alloc(8 * (size_t)n);
+  {
+    KernelTimer kt(s, "str_fn_hash", (double)total + 16.0 * (double)n);
+    hipLaunchKernelGGL(k_str_hash, grid, block, 0, s->stream, (const int64_t *)roff->p, (const uint8_t *)rbytes->p,
+                       (int64_t)0, n, (uint64_t *)rhash->p);
+    KERNEL_CHECK();
+  }
+  {
+    KernelTimer kt(s, "str_fn_probe", (double)total + 33.0 * (double)n);
+    hipLaunchKernelGGL(k_fn_probe, grid, block, 0, s->stream, (const int64_t *)ix.tab->p, (uint64_t)ix.slots - 1,
+                       (const uint64_t *)ix.hashes->p, off, bytes, dsrc, c0, n, (const uint8_t *)st->p,
+                       (const uint64_t *)rhash->p, (const int64_t *)roff->p, (const uint8_t *)rbytes->p,
+                       (int64_t *)d_out->p);
+    KERNEL_CHECK();
+  }
+  const size_t slots2 = (size_t)pow2_at_least(2 * (uint64_t)n);
+  BufPtr tab2 = s->alloc(8 * slots2), rep = s->alloc(8 * slots2), flag = s->alloc(8 * (size_t)n),
+         rank = s->alloc(8 * (size_t)n);
+  HIP_CHECK(hipMemsetAsync(tab2->p, 0xFF, 8 * slots2, s->stream));
+  HIP_CHECK(hipMemsetAsync(rep->p, 0xFF, 8 * slots2, s->stream));
+  {
+    KernelTimer kt(s, "str_fn_group", (double)total + 40.0 * (double)n);
+    hipLaunchKernelGGL(k_fn_group, grid, block, 0, s->stream, (int64_t *)tab2->p, (uint64_t)slots2 - 1,
+                       (unsigned long long *)rep->p, n, (const int64_t *)d_out->p, (const uint64_t *)rhash->p,
+                       (const int64_t *)roff->p, (const uint8_t *)rbytes->p, (int64_t *)grp->p);
+    KERNEL_CHECK();
+    hipLaunchKernelGGL(k_fn_rep_flags, grid, block, 0, s->stream, n, (const int64_t *)d_out->p,
+                       (const int64_t *)grp->p, (const unsigned long long *)rep->p, (int64_t *)flag->p);
+    KERNEL_CHECK();
+  }
+  const int64_t n_new = exclusive_scan_i64(s, (const int64_t *)flag->p, (int64_t *)rank->p, n);
+  std::vector<int64_t> codes;
+  if (n_new > 0) {
+    BufPtr items = s->alloc(8 * (size_t)n_new), nlen = s->alloc(8 * (size_t)(n_new + 1)),
+           noff = s->alloc(8 * (size_t)(n_new + 1));
+    HIP_CHECK(hipMemsetAsync((int64_t *)nlen->p + n_new, 0, 8, s->stream));
+    hipLaunchKernelGGL(k_fn_assign, grid, block, 0, s->stream, n, (int64_t)n0, (const int64_t *)grp->p,
+                       (const unsigned long long *)rep->p, (const int64_t *)rank->p, (const int64_t *)roff->p,
+                       (int64_t *)d_out->p, (int64_t *)items->p, (int64_t *)nlen->p);
+    KERNEL_CHECK();
+    const int64_t nb = exclusive_scan_i64(s, (const int64_t *)nlen->p, (int64_t *)noff->p, n_new + 1);
+    // staged as the heap will hold them: [n_new end offsets][nb bytes], one copy to the host
+    const size_t sbytes_at = 8 * (size_t)n_new, stage_size = sbytes_at + (((size_t)nb + 3) & ~(size_t)3);
+    BufPtr stage = s->alloc(stage_size + 8);
+    {
+      KernelTimer kt(s, "str_fn_append", 2.0 * (double)nb + 24.0 * (double)n_new);
+      hipLaunchKernelGGL(k_fn_stage, dim3(grid_for(std::max<int64_t>((nb + 3) / 4, n_new), SF_BLOCK)), block, 0,
+                         s->stream, n_new, nb, h.nbytes, (const int64_t *)noff->p, (const int64_t *)items->p,
+                         (const int64_t *)roff->p, (const uint8_t *)rbytes->p, (int64_t *)stage->p,
+                         (uint8_t *)stage->p + sbytes_at);
+      KERNEL_CHECK();
+    }
+    std::vector<char> host(stage_size);
+    HIP_CHECK(hipMemcpyAsync(host.data(), stage->p, stage_size, hipMemcpyDeviceToHost, s->stream));
+    if (out) HIP_CHECK(hipMemcpyAsync(out, d_out->p, 8 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    s->sync();
+    string_heap_append(s, n0, h.nbytes, (const int64_t *)stage->p, (const uint8_t *)stage->p + sbytes_at,
+                       (const int64_t *)host.data(), host.data() + sbytes_at, n_new, nb, codes);
+    // codes other than n0 + rank: another thread interned meanwhile (the host map resolved them)
+    bool moved = false;
+    for (int64_t r = 0; r < n_new; ++r) moved |= codes[(size_t)r] != (int64_t)n0 + r;
+    if (moved) {
+      std::vector<int64_t> tmp;
+      int64_t *o = out;
+      if (!o) {  // the device codes take the same correction, through the host
+        tmp.resize((size_t)n);
+        o = tmp.data();
+        HIP_CHECK(hipMemcpyAsync(o, d_out->p, 8 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+        s->sync();
+      }
+      for (int64_t i = 0; i < n; ++i)
+        if (o[i] >= (int64_t)n0) o[i] = codes[(size_t)(o[i] - (int64_t)n0)];
+      if (!out) {
+        HIP_CHECK(hipMemcpyAsync(d_out->p, o, 8 * (size_t)n, hipMemcpyHostToDevice, s->stream));
+        s->sync();  // (pageable source)
+      }
+    }
+    return d_out;
+  }
+  if (out) {
+    HIP_CHECK(hipMemcpyAsync(out, d_out->p, 8 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    s->sync();
+  }
+  return d_out;
+}
+
 void string_fn_codes(Session *s, int32_t fn, int64_t iarg0, int64_t iarg1, int64_t lit0, int64_t lit1,
                      const int64_t *src, int64_t c0, int64_t n, int64_t *out) {
   if (fn < CAPF_STR_FN_UPPER || fn > CAPF_STR_FN_REPLACE) illegal("unknown string function");
@@ -661,77 +767,276 @@ void string_fn_codes(Session *s, int32_t fn, int64_t iarg0, int64_t iarg1, int64
     }
   }
 
-  // ---- interning against the n0 strings of the snapshot
-  ensure_index(s, h, n0);
-  const Session::StrIndex &ix = s->str_index;
-  BufPtr rhash = s->alloc(8 * (size_t)n), d_out = s->alloc(8 * (size_t)n), grp = s->alloc(8 * (size_t)n);
-  {
-    KernelTimer kt(s, "str_fn_hash", (double)total + 16.0 * (double)n);
-    hipLaunchKernelGGL(k_str_hash, grid, block, 0, s->stream, (const int64_t *)roff->p, (const uint8_t *)rbytes->p,
-                       (int64_t)0, n, (uint64_t *)rhash->p);
-    KERNEL_CHECK();
-  }
-  {
-    KernelTimer kt(s, "str_fn_probe", (double)total + 33.0 * (double)n);
-    hipLaunchKernelGGL(k_fn_probe, grid, block, 0, s->stream, (const int64_t *)ix.tab->p, (uint64_t)ix.slots - 1,
-                       (const uint64_t *)ix.hashes->p, off, bytes, dsrc, c0, n, (const uint8_t *)st->p,
-                       (const uint64_t *)rhash->p, (const int64_t *)roff->p, (const uint8_t *)rbytes->p,
-                       (int64_t *)d_out->p);
-    KERNEL_CHECK();
-  }
-  const size_t slots2 = (size_t)pow2_at_least(2 * (uint64_t)n);
-  BufPtr tab2 = s->alloc(8 * slots2), rep = s->alloc(8 * slots2), flag = s->alloc(8 * (size_t)n),
-         rank = s->alloc(8 * (size_t)n);
-  HIP_CHECK(hipMemsetAsync(tab2->p, 0xFF, 8 * slots2, s->stream));
-  HIP_CHECK(hipMemsetAsync(rep->p, 0xFF, 8 * slots2, s->stream));
-  {
-    KernelTimer kt(s, "str_fn_group", (double)total + 40.0 * (double)n);
-    hipLaunchKernelGGL(k_fn_group, grid, block, 0, s->stream, (int64_t *)tab2->p, (uint64_t)slots2 - 1,
-                       (unsigned long long *)rep->p, n, (const int64_t *)d_out->p, (const uint64_t *)rhash->p,
-                       (const int64_t *)roff->p, (const uint8_t *)rbytes->p, (int64_t *)grp->p);
-    KERNEL_CHECK();
-    hipLaunchKernelGGL(k_fn_rep_flags, grid, block, 0, s->stream, n, (const int64_t *)d_out->p,
-                       (const int64_t *)grp->p, (const unsigned long long *)rep->p, (int64_t *)flag->p);
-    KERNEL_CHECK();
-  }
-  const int64_t n_new = exclusive_scan_i64(s, (const int64_t *)flag->p, (int64_t *)rank->p, n);
-  std::vector<int64_t> codes;
-  if (n_new > 0) {
-    BufPtr items = s->alloc(8 * (size_t)n_new), nlen = s->alloc(8 * (size_t)(n_new + 1)),
-           noff = s->alloc(8 * (size_t)(n_new + 1));
-    HIP_CHECK(hipMemsetAsync((int64_t *)nlen->p + n_new, 0, 8, s->stream));
-    hipLaunchKernelGGL(k_fn_assign, grid, block, 0, s->stream, n, (int64_t)n0, (const int64_t *)grp->p,
-                       (const unsigned long long *)rep->p, (const int64_t *)rank->p, (const int64_t *)roff->p,
-                       (int64_t *)d_out->p, (int64_t *)items->p, (int64_t *)nlen->p);
-    KERNEL_CHECK();
-    const int64_t nb = exclusive_scan_i64(s, (const int64_t *)nlen->p, (int64_t *)noff->p, n_new + 1);
-    // staged as the heap will hold them: [n_new end offsets][nb bytes], one copy to the host
-    const size_t sbytes_at = 8 * (size_t)n_new, stage_size = sbytes_at + (((size_t)nb + 3) & ~(size_t)3);
-    BufPtr stage = s->alloc(stage_size + 8);
-    {
-      KernelTimer kt(s, "str_fn_append", 2.0 * (double)nb + 24.0 * (double)n_new);
-      hipLaunchKernelGGL(k_fn_stage, dim3(grid_for(std::max<int64_t>((nb + 3) / 4, n_new), SF_BLOCK)), block, 0,
-                         s->stream, n_new, nb, h.nbytes, (const int64_t *)noff->p, (const int64_t *)items->p,
-                         (const int64_t *)roff->p, (const uint8_t *)rbytes->p, (int64_t *)stage->p,
-                         (uint8_t *)stage->p + sbytes_at);
-      KERNEL_CHECK();
+  intern_results(s, h, n0, dsrc, c0, n, st, roff, rbytes, total, out);
+}
+
+// ------------------------------------------------------------ split
+// split(subject, delimiter) per ROW of a table (capf_table_str_split): the
+// subject's bytes between the leftmost non-overlapping occurrences of a plain
+// (non-empty, literal) delimiter, as a LIST<STRING> column.
+//   count pass  per row: NULL or not, pieces = matches + 1, piece bytes =
+//               subject bytes − matches · delimiter bytes;
+//   two scans   the list offsets and each row's byte base in a scratch heap;
+//   write pass  the row's pieces back to back from its base (its subject with
+//               the delimiters removed) and one start offset per piece;
+//   interning   of the pieces (intern_results): the codes are the child column.
+// Thread tier: one thread walks the row with match_at.  Wave tier (a subject of
+// at least L bytes, on a worklist filled by the count pass and used by both
+// passes): lanes test one start position each over a 64-byte window, a ballot
+// gives the candidates, and the leftmost non-overlapping ones are picked from
+// the mask in wave-uniform code — the next free position carried across
+// windows, since a delimiter such as "aa" overlaps itself and a match may end
+// in the next window.
+// Profiled bytes, S = the bytes of the subjects of non-NULL rows, T = the piece
+// bytes, P = the pieces, n = the rows, w = the worklist's rows:
+//   str_split_count       S + 41 n   (two codes, one offset in; count, bytes, validity out)
+//   str_split_long_count  41 w
+//   str_split_write       S + T + 8 P + 40 n   (codes, offset, list offset, byte base in)
+//   str_split_long_write  40 w
+struct SplitArgs {
+  ColView s, d;  // subject and delimiter (STRING codes)
+  int64_t n0;    // dictionary strings of the heap snapshot
+};
+constexpr uint32_t SPLIT_ERR_EMPTY = 1;
+
+// Row r's subject bytes[q, q + slen) and delimiter; false: a NULL row.
+__device__ inline bool split_row(const SplitArgs &g, const int64_t *off, int64_t r, int64_t &q, int64_t &slen,
+                                 PatRef &p) {
+  if ((g.s.valid && !g.s.valid[r]) || (g.d.valid && !g.d.valid[r])) return false;
+  const int64_t cs = ld_int(g.s, r), cd = ld_int(g.d, r);
+  if (cs < 0 || cs >= g.n0 || cd < 0 || cd >= g.n0) return false;
+  q = off[cs];
+  slen = off[cs + 1] - q;
+  p = PatRef{nullptr, off[cd], off[cd + 1] - off[cd]};
+  return true;
+}
+
+__global__ __launch_bounds__(SF_BLOCK) void k_split_count(const int64_t *off, const uint8_t *bytes, SplitArgs g,
+                                                           int64_t n, int64_t long_len, int64_t *cnt, int64_t *blen,
+                                                           uint8_t *valid, uint32_t *err, int64_t *work,
+                                                           unsigned long long *nwork) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
+    int64_t q = 0, slen = 0, pieces = 0, nb = 0;
+    PatRef p{nullptr, 0, 0};
+    const bool ok = split_row(g, off, r, q, slen, p);
+    if (ok && p.len == 0) {
+      atomicOr(err, SPLIT_ERR_EMPTY);
+    } else if (ok && slen >= long_len) {
+      work[atomicAdd(nwork, 1ull)] = r;  // (counted by k_split_long_count)
+    } else if (ok) {
+      int64_t hits = 0;
+      for (int64_t k = 0; k + p.len <= slen;) {
+        if (match_at(bytes, q + k, p)) {
+          ++hits;
+          k += p.len;
+        } else {
+          ++k;
+        }
+      }
+      pieces = hits + 1;
+      nb = slen - hits * p.len;
     }
-    std::vector<char> host(stage_size);
-    HIP_CHECK(hipMemcpyAsync(host.data(), stage->p, stage_size, hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipMemcpyAsync(out, d_out->p, 8 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
-    s->sync();
-    string_heap_append(s, n0, h.nbytes, (const int64_t *)stage->p, (const uint8_t *)stage->p + sbytes_at,
-                       (const int64_t *)host.data(), host.data() + sbytes_at, n_new, nb, codes);
-    // codes other than n0 + rank: another thread interned meanwhile (the host map resolved them)
-    bool moved = false;
-    for (int64_t r = 0; r < n_new; ++r) moved |= codes[(size_t)r] != (int64_t)n0 + r;
-    if (moved)
-      for (int64_t i = 0; i < n; ++i)
-        if (out[i] >= (int64_t)n0) out[i] = codes[(size_t)(out[i] - (int64_t)n0)];
-    return;
+    cnt[r] = pieces;
+    blen[r] = nb;
+    if (valid) valid[r] = ok ? 1 : 0;
   }
-  HIP_CHECK(hipMemcpyAsync(out, d_out->p, 8 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+}
+
+// One wave over a subject: the matches picked window by window.  WRITE: the
+// pieces go to rbytes from w on, piece e + j's start to poff[e + j].
+template <bool WRITE>
+__device__ inline int64_t split_wave(const uint8_t *bytes, int64_t q, int64_t slen, const PatRef &p, int lane,
+                                     uint8_t *rbytes, int64_t w, int64_t *poff, int64_t e) {
+  int64_t hits = 0, next_free = 0, ps = 0;  // ps: where the open piece starts
+  if (WRITE && lane == 0) poff[e] = w;
+  for (int64_t base = 0; base + p.len <= slen; base += WAVE) {
+    const int64_t pos = base + lane;
+    uint64_t m = __ballot(pos + p.len <= slen && match_at(bytes, q + pos, p));
+    if (next_free > base) m = next_free - base >= WAVE ? 0 : m & ~((1ull << (next_free - base)) - 1ull);
+    while (m) {  // (wave-uniform)
+      const int64_t at = base + (__ffsll((unsigned long long)m) - 1);
+      ++hits;
+      if (WRITE) {
+        copy_wave(rbytes, w, bytes, q + ps, at - ps, 0, lane);
+        w += at - ps;
+        ps = at + p.len;
+        if (lane == 0) poff[e + hits] = w;
+      }
+      next_free = at + p.len;
+      m = next_free - base >= WAVE ? 0 : m & ~((1ull << (next_free - base)) - 1ull);
+    }
+  }
+  if (WRITE) copy_wave(rbytes, w, bytes, q + ps, slen - ps, 0, lane);
+  return hits;
+}
+
+__global__ __launch_bounds__(SF_BLOCK) void k_split_long_count(const int64_t *off, const uint8_t *bytes, SplitArgs g,
+                                                                const int64_t *work, int64_t nwork, int64_t *cnt,
+                                                                int64_t *blen) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  const int64_t nwaves = (int64_t)gridDim.x * blockDim.x / WAVE;
+  for (int64_t wi = wave; wi < nwork; wi += nwaves) {
+    const int64_t r = work[wi];
+    int64_t q = 0, slen = 0;
+    PatRef p{nullptr, 0, 0};
+    split_row(g, off, r, q, slen, p);
+    const int64_t hits = split_wave<false>(bytes, q, slen, p, lane, nullptr, 0, nullptr, 0);
+    if (lane == 0) {
+      cnt[r] = hits + 1;
+      blen[r] = slen - hits * p.len;
+    }
+  }
+}
+
+// loff: the list offsets [n + 1]; rbase: the rows' byte bases in rbytes; poff: the pieces' start offsets
+__global__ __launch_bounds__(SF_BLOCK) void k_split_write(const int64_t *off, const uint8_t *bytes, SplitArgs g,
+                                                           int64_t n, int64_t long_len, const int64_t *loff,
+                                                           const int64_t *rbase, uint8_t *rbytes, int64_t *poff) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
+    int64_t e = loff[r], q = 0, slen = 0;
+    if (loff[r + 1] == e) continue;  // a NULL row
+    PatRef p{nullptr, 0, 0};
+    split_row(g, off, r, q, slen, p);
+    if (slen >= long_len) continue;  // k_split_long_write's
+    int64_t w = rbase[r], ps = 0;
+    poff[e] = w;
+    for (int64_t k = 0; k + p.len <= slen;) {
+      if (match_at(bytes, q + k, p)) {
+        copy_thread(rbytes, w, bytes, q + ps, k - ps, 0);
+        w += k - ps;
+        k += p.len;
+        ps = k;
+        poff[++e] = w;
+      } else {
+        ++k;
+      }
+    }
+    copy_thread(rbytes, w, bytes, q + ps, slen - ps, 0);
+  }
+}
+
+__global__ __launch_bounds__(SF_BLOCK) void k_split_long_write(const int64_t *off, const uint8_t *bytes, SplitArgs g,
+                                                                const int64_t *work, int64_t nwork,
+                                                                const int64_t *loff, const int64_t *rbase,
+                                                                uint8_t *rbytes, int64_t *poff) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  const int64_t nwaves = (int64_t)gridDim.x * blockDim.x / WAVE;
+  for (int64_t wi = wave; wi < nwork; wi += nwaves) {
+    const int64_t r = work[wi];
+    int64_t q = 0, slen = 0;
+    PatRef p{nullptr, 0, 0};
+    split_row(g, off, r, q, slen, p);
+    split_wave<true>(bytes, q, slen, p, lane, rbytes, rbase[r], poff, loff[r]);
+  }
+}
+
+// S of the header: the subjects' bytes over the rows neither operand makes NULL (profiling only)
+static double split_source_bytes(Session *s, const SplitArgs &g, int64_t n) {
+  auto host_view = [&](const ColView &v, std::vector<uint8_t> &data, std::vector<uint8_t> &valid) {
+    const size_t w = v.enc == ENC_FOR32 ? 4 : v.enc == ENC_FOR24 ? 3 : 8;
+    data.resize(w * (size_t)n);
+    HIP_CHECK(hipMemcpyAsync(data.data(), v.data, data.size(), hipMemcpyDeviceToHost, s->stream));
+    if (v.valid) {
+      valid.resize((size_t)n);
+      HIP_CHECK(hipMemcpyAsync(valid.data(), v.valid, (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    }
+    s->sync();
+    ColView hv = v;
+    hv.data = data.data();
+    hv.valid = v.valid ? valid.data() : nullptr;
+    return hv;
+  };
+  std::vector<uint8_t> b0, b1, b2, b3;
+  const ColView hs = host_view(g.s, b0, b1), hd = host_view(g.d, b2, b3);
+  double by = 0;
+  std::lock_guard<std::mutex> lk(s->str_mu);
+  for (int64_t r = 0; r < n; ++r) {
+    if ((hs.valid && !hs.valid[r]) || (hd.valid && !hd.valid[r])) continue;
+    const int64_t c = ld_int(hs, r);
+    if (c >= 0 && c < g.n0) by += (double)s->strings[(size_t)c].size();
+  }
+  return by;
+}
+
+ColPtr str_split_column(Session *s, const Data &d, int subject_col, int delim_col) {
+  const int64_t n = d.nrows;
+  const ColPtr &sc = d.cols[(size_t)subject_col], &dc = d.cols[(size_t)delim_col];
+  auto o = std::make_shared<Column>();
+  o->type = Type::List;
+  o->n = n;
+  o->data = s->alloc(8 * (size_t)(n + 1));
+  HIP_CHECK(hipMemsetAsync(o->data->p, 0, 8 * (size_t)(n + 1), s->stream));
+  o->child = make_column(s, Type::String, 0, false);
+  if (n == 0) return o;
+  SplitArgs g{view_of(sc), view_of(dc), 0};
+  std::lock_guard<std::mutex> index_lock(s->index_mu);
+  size_t n0 = 0;
+  const StringHeap h = string_heap(s, &n0);  // the snapshot the whole step works against
+  g.n0 = (int64_t)n0;
+  const double src_bytes = s->profiling ? split_source_bytes(s, g, n) : 0;
+  const int64_t long_len = string_long_threshold();
+  const int64_t *off = (const int64_t *)h.off->p;
+  const uint8_t *bytes = (const uint8_t *)h.bytes->p;
+  const int waves_per_block = SF_BLOCK / WAVE;
+  const dim3 grid(grid_for(n, SF_BLOCK)), block(SF_BLOCK);
+  int64_t *loff = (int64_t *)o->data->p;
+
+  BufPtr cnt = s->alloc(8 * (size_t)(n + 1)), blen = s->alloc(8 * (size_t)(n + 1)),
+         rbase = s->alloc(8 * (size_t)(n + 1)), work = s->alloc(8 * (size_t)n), ctr = s->alloc(16);
+  BufPtr valid = g.s.valid || g.d.valid ? s->alloc((size_t)n) : nullptr;
+  HIP_CHECK(hipMemsetAsync(ctr->p, 0, 16, s->stream));  // [0] the worklist's length, [1] the error flags
+  HIP_CHECK(hipMemsetAsync((int64_t *)cnt->p + n, 0, 8, s->stream));
+  HIP_CHECK(hipMemsetAsync((int64_t *)blen->p + n, 0, 8, s->stream));
+  {
+    KernelTimer kt(s, "str_split_count", src_bytes + 41.0 * (double)n);
+    hipLaunchKernelGGL(k_split_count, grid, block, 0, s->stream, off, bytes, g, n, long_len, (int64_t *)cnt->p,
+                       (int64_t *)blen->p, valid ? (uint8_t *)valid->p : nullptr, (uint32_t *)((int64_t *)ctr->p + 1),
+                       (int64_t *)work->p, (unsigned long long *)ctr->p);
+    KERNEL_CHECK();
+  }
+  HIP_CHECK(hipMemcpyAsync(s->h_scalars, ctr->p, 16, hipMemcpyDeviceToHost, s->stream));
   s->sync();
+  const int64_t nwork = s->h_scalars[0];
+  if (s->h_scalars[1] & SPLIT_ERR_EMPTY) illegal("split() with an empty delimiter");
+  if (nwork > 0) {
+    KernelTimer kt(s, "str_split_long_count", 41.0 * (double)nwork);
+    hipLaunchKernelGGL(k_split_long_count, dim3(grid_for(nwork, waves_per_block)), block, 0, s->stream, off, bytes, g,
+                       (const int64_t *)work->p, nwork, (int64_t *)cnt->p, (int64_t *)blen->p);
+    KERNEL_CHECK();
+  }
+  const int64_t npieces = exclusive_scan_i64(s, (const int64_t *)cnt->p, loff, n + 1);
+  const int64_t total = exclusive_scan_i64(s, (const int64_t *)blen->p, (int64_t *)rbase->p, n + 1);
+  o->valid = valid;
+  if (npieces == 0) return o;  // NULL rows only
+  // the scratch result heap, padded like the string heap (words covering a string are read)
+  BufPtr rbytes = s->alloc((size_t)total + 16), poff = s->alloc(8 * (size_t)(npieces + 1));
+  {
+    KernelTimer kt(s, "str_split_write",
+                   src_bytes + (double)total + 8.0 * (double)npieces + 40.0 * (double)n);
+    hipLaunchKernelGGL(k_split_write, grid, block, 0, s->stream, off, bytes, g, n, long_len, (const int64_t *)loff,
+                       (const int64_t *)rbase->p, (uint8_t *)rbytes->p, (int64_t *)poff->p);
+    KERNEL_CHECK();
+  }
+  if (nwork > 0) {
+    KernelTimer kt(s, "str_split_long_write", 40.0 * (double)nwork);
+    hipLaunchKernelGGL(k_split_long_write, dim3(grid_for(nwork, waves_per_block)), block, 0, s->stream, off, bytes, g,
+                       (const int64_t *)work->p, nwork, (const int64_t *)loff, (const int64_t *)rbase->p,
+                       (uint8_t *)rbytes->p, (int64_t *)poff->p);
+    KERNEL_CHECK();
+  }
+  HIP_CHECK(hipMemcpyAsync((int64_t *)poff->p + npieces, (const int64_t *)rbase->p + n, 8, hipMemcpyDeviceToDevice,
+                           s->stream));
+  // every piece has bytes (ST_BYTES = 0): none is NULL, an identity or the host's
+  BufPtr st = s->alloc((size_t)npieces);
+  HIP_CHECK(hipMemsetAsync(st->p, ST_BYTES, (size_t)npieces, s->stream));
+  auto child = std::make_shared<Column>();
+  child->type = Type::String;
+  child->n = npieces;
+  child->data = intern_results(s, h, n0, nullptr, 0, npieces, st, poff, rbytes, total, nullptr);
+  o->child = child;
+  return o;
 }
 
 }  // namespace capf

@@ -532,6 +532,67 @@ def device_string_fn(key, intern):
 
 
 @dataclass(frozen=True)
+class Split(Expr):
+    """split(original, delimiter) (okapi Split, Expr.scala:904-912; Morpheus
+    StringSplit, SparkSQLExprMapper.scala:272; expectations FunctionTests.scala:
+    1721-1746): two STRING operands give LIST<STRING>, a NULL operand a NULL
+    list, elements are never NULL.  The value is Spark 2.4.3's StringSplit
+    (build.params.gradle:21), java.lang.String.split(regex, -1) — `split_fn`.
+    A table operation (table.py `_hoist_lists`): a plain delimiter
+    (`plain_split_delimiter`) is split on the device string heap
+    (capf_table_str_split), any other on the host per distinct pair."""
+    original: Expr
+    delimiter: Expr
+
+    def __str__(self):
+        return f"split({self.original}, {self.delimiter})"
+
+
+def split_fn(s, d):
+    """java.lang.String.split(d, -1) of s — d a regex, trailing empty strings
+    kept: the pieces between the matches plus the tail, a zero-width match at
+    index 0 skipped (so split_fn("abc", "") is ["a", "b", "c", ""]); without a
+    match [s].  None when an operand is None."""
+    import re
+    if s is None or d is None:
+        return None
+    out, at = [], 0
+    for m in re.finditer(d, s):
+        if m.end() == 0:  # a zero-width match at index 0 gives no leading ""
+            continue
+        out.append(s[at:m.start()])
+        at = m.end()
+    return out + [s[at:]]
+
+
+def fold_split(e, params=None):
+    """The literal a Split of two literal / parameter operands folds to at
+    plan time — a ListLit of its pieces, NullLit for a NULL operand — else
+    None (an operand is per row, or no string)."""
+    vals = []
+    for x in (e.original, e.delimiter):
+        if isinstance(x, Param):
+            x = literal_expr((params or {}).get(x.pname)) if not isinstance(
+                (params or {}).get(x.pname), (list, tuple, dict)) else x
+        if isinstance(x, StringLit):
+            vals.append(x.v)
+        elif isinstance(x, NullLit):
+            vals.append(None)
+        else:
+            return None
+    r = split_fn(*vals)
+    return NullLit() if r is None else ListLit(*[StringLit(p) for p in r])
+
+
+def plain_split_delimiter(d):
+    """True when split's delimiter matches exactly its own text wherever Java
+    would match it — non-empty, no regex metacharacter (plain_replace_literal)
+    and no lone surrogate (WTF-8 bytes of one could match inside a pair's
+    4-byte sequence) — so the device may search byte for byte."""
+    return plain_replace_literal(d) and not any(0xD800 <= ord(ch) <= 0xDFFF for ch in d)
+
+
+@dataclass(frozen=True)
 class ContainerIndex(Expr):
     """container[index] (okapi ContainerIndex, Expr.scala:1240; Flink
     `container.at(index)`, FlinkSQLExprMapper.scala:262-269) on a list: the
@@ -558,7 +619,7 @@ class ContainerIndex(Expr):
 Head = _unary("Head", "head({})")
 Last = _unary("Last", "last({})")
 # reverse(xs) (:265): the elements in reverse order, NULL elements included; a
-# NULL list gives NULL.  reverse of a STRING (and split) is NotImplemented.
+# NULL list gives NULL.  reverse of a STRING is NotImplemented.
 Reverse = _unary("Reverse", "reverse({})")
 
 
@@ -667,7 +728,7 @@ def may_hold_list_fn(e):
     try:
         return e.__dict__["_lf"]
     except KeyError:
-        k = e.__dict__["_lf"] = (isinstance(e, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo))
+        k = e.__dict__["_lf"] = (isinstance(e, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo, Split))
                                  or isinstance(e, LAMBDA_EXPRS)
                                  or type(e).__name__ == "Add"
                                  or any(isinstance(x, ListLit) or may_hold_list_fn(x) for x in sub_exprs(e)))
@@ -677,8 +738,8 @@ def may_hold_list_fn(e):
 def list_valued(e, header, columns, params=None, coltype=None):
     """Is e a list-valued expression the table operations project to a
     temporary LIST column before the rest is lowered: Reverse, Range, a slice,
-    or an Add whose static type is LIST."""
-    if isinstance(e, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo)):
+    split, or an Add whose static type is LIST."""
+    if isinstance(e, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo, Split)):
         return True
     if isinstance(e, LAMBDA_EXPRS):  # hoisted too: a LIST temporary, or a scalar one (a quantifier, reduce)
         return True
@@ -813,7 +874,7 @@ def check_lambda_body(body, owner):
         what = None
         if isinstance(x, LAMBDA_EXPRS):
             what = "a lambda expression inside a lambda body (nested lists)"
-        elif isinstance(x, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo)):
+        elif isinstance(x, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo, Split)):
             what = "a list-valued sub-expression inside a lambda body"
         elif isinstance(x, ListLit) and x is not body and any(
                 not isinstance(i, (IntegerLit, FloatLit, StringLit, BoolLit, NullLit, Param)) for i in x.items):
@@ -1338,6 +1399,9 @@ def _static_type(e, header, columns, params=None, coltype=None):
         return T_BOOL
     if type(e).__name__ in _STR_FUNCS or isinstance(e, (Substring, Replace, ToString)):
         return T_STRING
+    if isinstance(e, Split):  # a NULL-typed operand: a NULL-typed column
+        ts = [_static_type(x, header, columns, params, coltype) for x in (e.original, e.delimiter)]
+        return T_NULL if T_NULL in ts else T_LIST
     if isinstance(e, (Reverse, Range, ListSliceFromTo, ListSliceFrom, ListSliceTo, ListComprehension, ListFilter)):
         return T_LIST
     if isinstance(e, (ListAny, ListAll, ListNone, ListSingle)):

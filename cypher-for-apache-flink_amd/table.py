@@ -511,6 +511,7 @@ class GpuTable:
             t, (expr2,), h2, tmps = self._hoist_lists([expr], header, params)
             if tmps:
                 return t.filter(expr2, header=h2, params=params).select(*self.physicalColumns)
+            expr = expr2  # (a split of literals folded)
         prog = _program(expr, header, self, params)
         e, keep = _lib._keepalive_expr(prog)
         return self._new("capf_table_filter", self._h, byref(e), cols=self._cols)
@@ -738,9 +739,12 @@ class GpuTable:
         predicate / body compiled against the table's columns with the lambda
         variable bound, and capf_table_list_lambda builds the temporary: a
         LIST for a comprehension or filter, a scalar for a quantifier or
-        reduce.  Without such a sub-expression nothing changes."""
-        from .expr import (LAMBDA_EXPRS, ListLit, check_lambda_body, lambda_parts, list_fn_args, list_valued,
-                           list_values, replace_exprs, sub_exprs)
+        reduce.  A split of two literals folds to a list literal (no
+        temporary: only the returned expressions change); any other split
+        becomes a temporary built by `_str_split`.  Without such a
+        sub-expression nothing changes."""
+        from .expr import (LAMBDA_EXPRS, ListLit, Split, check_lambda_body, fold_split, lambda_parts, list_fn_args,
+                           list_valued, list_values, replace_exprs, sub_exprs)
         t, h, m, tmps = self, header, {}, []
         cols = set(self.physicalColumns)
 
@@ -789,7 +793,15 @@ class GpuTable:
             e2 = replace_exprs(e, m)
             c = tmp()
             ctype = "LIST"
-            if isinstance(e2, ListLit):
+            if isinstance(e2, Split):
+                lit = fold_split(e2, params)
+                if lit is not None:  # both operands literal: a list literal at plan time, no column
+                    tmps.pop()
+                    m[e] = lit
+                    continue
+                str_col, delim_col = column_of(e2.original), column_of(e2.delimiter)  # (may extend t)
+                t = t._str_split(e2, c, str_col, delim_col)
+            elif isinstance(e2, ListLit):
                 t = t.withColumns((e2, c), header=h, params=params)
             elif isinstance(e2, LAMBDA_EXPRS):
                 _, lst, _, _, init, _ = lambda_parts(e2)
@@ -807,6 +819,47 @@ class GpuTable:
                 h = RecordHeader({})
             h = h.with_expr(v, c) if hasattr(h, "with_expr") else {**h, v: c}
         return t, [replace_exprs(e, m) for e in exprs], h, tmps
+
+    def _str_split(self, e, name, str_col, delim_col):
+        """This table plus column `name` = split(str_col, delim_col) (expr.Split).
+        Device route (capf_table_str_split): every distinct non-NULL delimiter
+        value is plain (expr.plain_split_delimiter) — a literal delimiter is a
+        constant column and decides like any other.  Host route otherwise (a
+        regex, the empty delimiter, a lone surrogate; CAPF_STR_SPLIT=host
+        forces it): expr.split_fn per distinct (subject, delimiter) pair, the
+        column built with add_list."""
+        from .expr import StringLit, plain_split_delimiter, split_fn
+        if getattr(self.session, "value_map_gather", None) is not None:
+            # distributed: each rank would intern different new strings and the dictionaries diverge
+            raise _lib.NotImplementedException(f"{e} on the distributed layer")
+        types = [self.capf_type(c) for c in (str_col, delim_col)]
+        if any(ty not in (T_STRING, T_NULL) for ty in types):
+            raise _lib.IllegalArgumentException(f"{e}: split takes two STRING operands")
+        host = False
+        if T_NULL not in types:
+            if isinstance(e.delimiter, StringLit):  # (the constant column's one value: nothing to download)
+                delims = [e.delimiter.v]
+            else:
+                dv, dok = self.select(delim_col).distinct(delim_col).column_arrays(delim_col)
+                delims = [self.session.lookup(int(c)) for c in dv[dok]]
+            host = os.environ.get("CAPF_STR_SPLIT") == "host" or not all(plain_split_delimiter(d) for d in delims)
+        if host:
+            (sv, sok), (dv, dok) = self.column_arrays(str_col), self.column_arrays(delim_col)
+            memo, values = {}, []
+            for a, b, ok in zip(sv.tolist(), dv.tolist(), (sok & dok).tolist()):
+                if not ok:
+                    values.append(None)
+                    continue
+                r = memo.get((a, b))
+                if r is None:
+                    r = memo[(a, b)] = split_fn(self.session.lookup(a), self.session.lookup(b))
+                values.append(r)
+            if memo:  # (no non-NULL row: the node below gives the NULL lists, typed LIST<STRING>)
+                return self.add_list(name, values)
+        # evaluated at once: the pieces are in the dictionary before any later program is compiled
+        # (a code map — toUpper(x) over the elements — covers the dictionary of its time)
+        return self._new("capf_table_str_split", self._h, str_col.encode(), delim_col.encode(),
+                         name.encode()).materialize()
 
     def _list_lambda(self, e, name, header, params, list_col, init_col):
         """(this table plus column `name` = the lambda expression e over LIST
@@ -860,6 +913,8 @@ class GpuTable:
                     out = t.withColumns(*zip(exprs, [c for _, c in columns]), header=h2, params=params)
                     gone = set(tmps)
                     return out.select(*[c for c in out.physicalColumns if c not in gone])
+                if exprs != [e for e, _ in columns]:  # a split of literals folded: no temporary
+                    return self.withColumns(*zip(exprs, [c for _, c in columns]), header=header, params=params)
                 break
         lit = [(e, c) for e, c in columns if _list_items(e, params) is not None]
         if lit:  # [x, y, ...] / $list: LIST columns of per-row elements (capf_table_list_columns)

@@ -822,6 +822,24 @@ capf_status capf_table_list_lambda(capf_table *t, int32_t kind, const char *list
                                    const char *init,       /* REDUCE: column name, else "" */
                                    int32_t out_type,       /* element / result capf type */
                                    const char *name, capf_table **out);
+/* split(original, delimiter) (okapi Split, Expr.scala:904-912; the Morpheus
+ * lowering StringSplit, SparkSQLExprMapper.scala:272; expectations
+ * FunctionTests.scala:1721-1746): this table plus LIST<STRING> column `name`,
+ * row i = the pieces of str_col[i] between the leftmost non-overlapping
+ * occurrences of delim_col[i], compared byte for byte on the device string
+ * heap: matches + 1 pieces, trailing and inner empty strings kept, a subject
+ * without a match one piece (itself; "" gives [""]).  That is what
+ * java.lang.String.split(regex, -1) computes for a delimiter that is non-empty
+ * and holds no regex metacharacter; the caller evaluates every other
+ * delimiter itself.  A NULL operand gives a NULL list; elements are never
+ * NULL.  The pieces are interned on the device (new codes ascend by the
+ * smallest piece position producing each string).
+ * The node is lazy and type-checked when built: both columns are STRING or
+ * NULL-typed (a NULL-typed one gives a NULL-typed column), anything else is
+ * IllegalArgument.  A row whose delimiter is the empty string is
+ * IllegalArgument, raised when the table is evaluated.                      */
+capf_status capf_table_str_split(capf_table *t, const char *str_col, const char *delim_col,
+                                 const char *name, capf_table **out);
 /* labels(n) / keys(n) (FlinkSQLExprMapper.scala:136-153; the GetLabels /
  * GetKeys UDFs, :310-329): appends LIST<STRING> column `name` holding, per row,
  * codes[j] for each column cols[j] that holds TRUE (kinds[j] = 0, a label flag)

@@ -584,6 +584,16 @@ JNI(jlong, tableListFn)(JNIEnv *env, jobject, jlong t, jint fn, jobjectArray arg
   capf_table *out = nullptr;
   return fail(env, capf_table_list_fn(T(t), (int32_t)fn, a.n(), a.data(), nm.p, &out)) ? 0 : H(out);
 }
+// split(strCol, delimCol) on the device string heap (okapi Expr.scala:904-912): a LIST<STRING> column
+JNI(jlong, tableStrSplit)(JNIEnv *env, jobject, jlong t, jstring strCol, jstring delimCol, jstring name) {
+  if (!strCol || !delimCol || !name) {
+    illegal_argument(env, "tableStrSplit: strCol, delimCol and name must not be null");
+    return 0;
+  }
+  JStr sc(env, strCol), dc(env, delimCol), nm(env, name);
+  capf_table *out = nullptr;
+  return fail(env, capf_table_str_split(T(t), sc.p, dc.p, nm.p, &out)) ? 0 : H(out);
+}
 // a lambda expression over a LIST column (okapi Expr.scala:199, 1178-1237); pred / body null = absent
 JNI(jlong, tableListLambda)(JNIEnv *env, jobject, jlong t, jint kind, jstring list, jobject pred, jobject body,
                             jstring init, jint outType, jstring name) {

@@ -428,6 +428,8 @@ object GpuExprMapper {
           case None => emit(LitNull, Native.TypeInt64)                    // expressions.Null(Types.LONG)
         }
         c.alternatives.reverse.foreach { case (p, v) => go(p); go(v); emit(If_) }
+      case sp: Split =>  // Expr.scala:904-912: a table operation (GpuTable.hoistLists builds the LIST column)
+        throw NotImplementedException(s"GPU split(${sp.original}, ${sp.delimiter}) outside withColumns / filter")
       case other =>
         throw NotImplementedException(s"No support for converting Cypher expression $other to a GPU expression")
     }

@@ -29,6 +29,20 @@ object GpuStringFunctions {
   def plainReplaceLiteral(search: String): Boolean =
     search.nonEmpty && !search.exists(ch => "\\^$.|?*+()[]{}".indexOf(ch) >= 0)
 
+  /** split's delimiter is a Java regex too (StringSplit = String.split(regex, -1)): true when it
+    * is non-empty, holds no metacharacter and no lone surrogate, so that the device may search
+    * byte for byte (the twin of expr.py plain_split_delimiter). */
+  def plainSplitDelimiter(d: String): Boolean =
+    plainReplaceLiteral(d) && !d.indices.exists { i =>
+      val ch = d.charAt(i)
+      Character.isSurrogate(ch) && !(
+        (Character.isHighSurrogate(ch) && i + 1 < d.length && Character.isLowSurrogate(d.charAt(i + 1))) ||
+          (Character.isLowSurrogate(ch) && i > 0 && Character.isHighSurrogate(d.charAt(i - 1))))
+    }
+
+  /** split(s, d) on the host: what Spark 2.4.3's StringSplit computes (the twin of expr.py split_fn). */
+  def split(s: String, d: String): Seq[String] = s.split(d, -1).toSeq
+
   private def trimSpaces(s: String, leading: Boolean, trailing: Boolean): String = {
     var b = 0
     var e = s.length

@@ -64,7 +64,8 @@ final class GpuTable private (private[gpu] val handle: Long)(implicit val sessio
   override def filter(expr: Expr)(implicit header: RecordHeader, parameters: CypherMap): GpuTable = { // :81
     val (t, Seq(e2), h2, tmps) = hoistLists(Seq(expr), header, parameters)
     if (tmps.nonEmpty) return t.filter(e2)(h2, parameters).select(physicalColumns: _*)
-    wrap(Native.tableFilter(handle, GpuExprMapper.program(expr, header, this, parameters)))
+    // (e2: a split of literals folded to a list literal)
+    wrap(Native.tableFilter(handle, GpuExprMapper.program(e2, header, this, parameters)))
   }
 
   override def drop(cols: String*): GpuTable = wrap(Native.tableDrop(handle, cols.toArray))   // :89
@@ -197,6 +198,50 @@ final class GpuTable private (private[gpu] val handle: Long)(implicit val sessio
         GpuTypes.fromCypher(outType), c))
       c
     }
+    // split(s, d) (okapi Expr.scala:904-912; table.py `_str_split`): both literal — a list literal at
+    // plan time; every distinct non-NULL delimiter plain — capf_table_str_split on the device string
+    // heap; else (a regex, the empty delimiter, a lone surrogate) String.split(d, -1) per distinct pair
+    // on the host and a column from host lists.
+    def literalString(x: Expr): Option[Option[String]] = x match {
+      case StringLit(v) => Some(Some(v))
+      case NullLit(_) => Some(None)
+      case Param(name) => parameters(name) match {
+        case CypherString(v) => Some(Some(v))
+        case CypherNull => Some(None)
+        case _ => None
+      }
+      case _ => None
+    }
+    def lowerSplit(sp: Split): Either[Expr, String] = (literalString(sp.original), literalString(sp.delimiter)) match {
+      case (Some(Some(s)), Some(Some(d))) =>
+        Left(ListLit(GpuStringFunctions.split(s, d).map(StringLit(_)).toList))
+      case (Some(a), Some(b)) if a.isEmpty || b.isEmpty => Left(NullLit())
+      case _ =>
+        import org.opencypher.okapi.api.types.CTString
+        val strCol = columnFor(sp.original)
+        val delimCol = columnFor(sp.delimiter)
+        val typed = Seq(strCol, delimCol).forall(c => t.columnType(c) == CTString || t.columnType(c) == CTString.nullable)
+        val pairs: Seq[(CypherValue, CypherValue)] =
+          if (!typed) Seq.empty
+          else GpuRows.download(t.select(strCol, delimCol)).map(r => (r(strCol), r(delimCol))).toSeq
+        val onHost = pairs.exists {
+          case (_, CypherString(d)) => !GpuStringFunctions.plainSplitDelimiter(d)
+          case _ => false
+        }
+        val c = tmp()
+        if (onHost && pairs.exists { case (CypherString(_), CypherString(_)) => true; case _ => false }) {
+          val memo = scala.collection.mutable.Map.empty[(String, String), CypherValue]
+          val lists = pairs.map {
+            case (CypherString(s), CypherString(d)) =>
+              memo.getOrElseUpdate((s, d), CypherList(GpuStringFunctions.split(s, d).map(CypherString(_)): _*))
+            case _ => CypherNull
+          }
+          t = wrap(GpuRows.addList(t, c, lists))
+        } else {
+          t = wrap(Native.tableStrSplit(t.handle, strCol, delimCol, c))
+        }
+        Right(c)
+    }
     def lower(e: Expr, top: Boolean): Expr = done.getOrElse(e, {
       val parts = lambdaParts(e)
       if (parts.isDefined) {
@@ -210,7 +255,17 @@ final class GpuTable private (private[gpu] val handle: Long)(implicit val sessio
       } else {
         val kids = e.children.map(c => lower(c, top = false))
         val e2 = if (kids.isEmpty || e.isInstanceOf[ListLit]) e else e.withNewChildren(kids.toArray)
-        val col: Option[String] = listFnArgs(e2) match {
+        val folded: Option[Expr] = e2 match {
+          case sp: Split => lowerSplit(sp) match {
+            case Left(lit) => Some(lit)
+            case Right(c) => Some(Var(c)(e2.cypherType))
+          }
+          case _ => None
+        }
+        val col: Option[String] = folded match {
+          case Some(v: Var) => Some(v.name)
+          case Some(_) => None
+          case None => listFnArgs(e2) match {
           case Some((fn, args)) =>
             val names = args.map {
               case None => ""
@@ -223,6 +278,7 @@ final class GpuTable private (private[gpu] val handle: Long)(implicit val sessio
           case None if !top && perRowLiteral(e2) =>
             val c = tmp(); t = t.withColumns(e2 -> c)(h, parameters); Some(c)
           case None => None
+          }
         }
         col match {
           case Some(c) =>
@@ -232,7 +288,7 @@ final class GpuTable private (private[gpu] val handle: Long)(implicit val sessio
             if (h.column(v) != c) t = t.select(t.physicalColumns.map(x => if (x == c) c -> h.column(v) else x -> x): _*)
             done += e -> v
             v
-          case None => e2
+          case None => folded.getOrElse(e2)
         }
       }
     })
@@ -246,6 +302,8 @@ final class GpuTable private (private[gpu] val handle: Long)(implicit val sessio
       val out = hoisted.withColumns(exprs.zip(columns.map(_._2)): _*)(h2, parameters)
       return out.select(out.physicalColumns.filterNot(tmps.contains): _*)
     }
+    if (exprs != columns.map(_._1))  // a split of literals folded: no temporary
+      return withColumns(exprs.zip(columns.map(_._2)): _*)
     val (literalLists, others) = columns.partition { case (e, _) => listItems(e, parameters).isDefined }
     if (literalLists.nonEmpty) {  // [x, y, ...] / $list (FlinkSQLExprMapper.scala:71, 75): capf_table_list_columns
       val base = if (others.isEmpty) this else withColumns(others: _*)

@@ -189,6 +189,8 @@ object Native {
   @native def tableListColumns(table: Long, cols: Array[String], name: String): Long
   // capf_table_list_fn: fn = ListFn*, args = column names ("" = an absent slice bound / step)
   @native def tableListFn(table: Long, fn: Int, args: Array[String], name: String): Long
+  // capf_table_str_split: split(strCol, delimCol) for plain delimiters (GpuStringFunctions.plainSplitDelimiter)
+  @native def tableStrSplit(table: Long, strCol: String, delimCol: String, name: String): Long
   // capf_table_list_lambda: kind = Lambda*, pred / body = null when absent, init = "" but for reduce
   @native def tableListLambda(table: Long, kind: Int, list: String, pred: Program, body: Program, init: String,
                               outType: Int, name: String): Long
