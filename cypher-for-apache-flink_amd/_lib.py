@@ -86,6 +86,7 @@ _SIGS = {
     "capf_session_profile_entry": (c_int32, [_S, c_int32, POINTER(c_char_p), POINTER(c_int64),
                                              POINTER(c_double), POINTER(c_double)]),
     "capf_session_last_plan": (c_char_p, [_S]),
+    "capf_session_last_plan_detail": (c_char_p, [_S]),
     "capf_string_intern": (c_int32, [_S, c_char_p, POINTER(c_int64)]),
     "capf_string_lookup": (c_int32, [_S, c_int64, POINTER(c_char_p)]),
     "capf_string_digest": (c_int32, [_S, POINTER(c_int64), POINTER(c_uint64)]),

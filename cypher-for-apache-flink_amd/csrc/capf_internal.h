@@ -407,6 +407,9 @@ struct Session {
   bool profiling = false;
   std::map<std::string, ProfileEntry> profile;
   std::string last_plan = "none";
+  // which messages and root kernel the last message-passing count used
+  // (fused_count.hip tree_count; DESIGN.md "Plan detail"); "" until one runs
+  std::string last_plan_detail;
   // string dictionary
   std::mutex str_mu;
   std::vector<std::string> strings;

@@ -34,6 +34,7 @@
 #include "capf_internal.h"
 #include "device_common.h"
 #include "join_graph.h"
+#include "key_range.h"
 
 namespace capf {
 
@@ -44,11 +45,13 @@ struct DMap {
   int32_t kind;
   int32_t pad;
   int64_t lo, hi;                 // dense / ones: key range [lo, hi]
-  unsigned long long *vals;       // dense: hi-lo+1 entries; hash: capacity entries
+  unsigned long long *vals;       // dense: hi-lo+1 entries; hash: capacity + 1 entries
   int64_t *keys;                  // hash keys (HASH_EMPTY = free)
   uint64_t mask;                  // hash capacity - 1
 };
 
+// A free hash slot holds HASH_EMPTY.  INT64_MIN is a legal id, so it never
+// enters the probe sequence: its weight lives in vals[capacity], past the slots.
 constexpr int64_t HASH_EMPTY = INT64_MIN;
 
 __device__ inline unsigned long long map_get(const DMap &m, int64_t k) {
@@ -61,6 +64,7 @@ __device__ inline unsigned long long map_get(const DMap &m, int64_t k) {
     const uint64_t o = (uint64_t)(k - m.lo);
     return (unsigned long long)((((const uint32_t *)m.vals)[o >> 5] >> (o & 31)) & 1u);
   }
+  if (k == HASH_EMPTY) return m.vals[m.mask + 1];
   uint64_t slot = fmix64((uint64_t)k) & m.mask;
   while (true) {
     int64_t cur = m.keys[slot];
@@ -76,6 +80,10 @@ __device__ inline void map_add(const DMap &m, int64_t k, unsigned long long w) {
     return;
   }
   if (m.kind != MAP_HASH) return;  // only dense and hash maps have storage
+  if (k == HASH_EMPTY) {
+    atomicAdd(&m.vals[m.mask + 1], w);
+    return;
+  }
   uint64_t slot = fmix64((uint64_t)k) & m.mask;
   while (true) {
     int64_t cur = m.keys[slot];
@@ -733,13 +741,18 @@ static Program eq_program(const std::string &a, const std::string &b) {
   return p;
 }
 
-LeafData leaf_data(const Leaf &lf) {
-  LeafData ld;
+// A leaf's plan: its base node under its pushed-down filters and intra-row equalities.
+static NodePtr leaf_plan(const Leaf &lf) {
   NodePtr cur = lf.node;
   for (auto &p : lf.filters) cur = filter_node(cur, p);
   for (auto &e : lf.col_eqs)
     cur = filter_node(cur, eq_program(lf.node->names[e.first], lf.node->names[e.second]));
-  ld.data = materialize(cur);
+  return cur;
+}
+
+LeafData leaf_data(const Leaf &lf) {
+  LeafData ld;
+  ld.data = materialize(leaf_plan(lf));
   ld.plain = lf.filters.empty() && lf.col_eqs.empty();
   return ld;
 }
@@ -792,12 +805,19 @@ __global__ void k_bits_set(ColView c, int64_t n, int64_t lo, int64_t hi, uint32_
     const uint64_t o = (uint64_t)(k - lo);
     const uint32_t w = live ? (uint32_t)(o >> 5) : 0xFFFFFFFFu;
     uint32_t bits = live ? 1u << (o & 31) : 0u, dupb = 0;
-    // segmented inclusive OR over lanes with equal words (disjoint coverage,
-    // so a bit seen twice is a duplicate key)
+    // segmented inclusive OR over each run of adjacent lanes with equal words
+    // (disjoint coverage, so a bit seen twice is a duplicate key).  A run ends
+    // where the word changes: lanes that share a word across another word
+    // (unsorted ids) are separate runs, each with its own atomic — merged by
+    // word alone their coverage would overlap and report duplicates of
+    // distinct keys
+    const uint32_t wp = __shfl_up(w, 1, WAVE);
+    const uint64_t heads = __ballot(lane == 0 || wp != w);
+    const int start = 63 - __clzll((long long)(heads & ((2ull << lane) - 1ull)));
 #pragma unroll
     for (int d = 1; d < WAVE; d <<= 1) {
-      const uint32_t wo = __shfl_up(w, d, WAVE), bo = __shfl_up(bits, d, WAVE), dbo = __shfl_up(dupb, d, WAVE);
-      if (lane >= d && wo == w) {
+      const uint32_t bo = __shfl_up(bits, d, WAVE), dbo = __shfl_up(dupb, d, WAVE);
+      if (lane - d >= start) {
         dupb |= dbo | (bo & bits);
         bits |= bo;
       }
@@ -812,11 +832,12 @@ __global__ void k_bits_set(ColView c, int64_t n, int64_t lo, int64_t hi, uint32_
 // The membership bitmap of `mykey` over the parent key's range: built once per
 // (column, range) and cached on the column (an ingest-time bitmap index of an
 // immutable id column, like the statistics), then reused by every query.
-static bool bits_map_for(Session *s, const ColPtr &parent_key, const ColPtr &mykey, HostMap &h) {
+static bool bits_map_for(Session *s, const ColPtr &parent_key, const ColPtr &mykey, HostMap &h,
+                         bool *was_cached) {
   const ColStats &st = column_stats(s, parent_key);
   if (st.non_null == 0 || mykey->type != Type::Int64) return false;
-  const uint64_t range = (uint64_t)(st.max - st.min) + 1;
-  if (range > (uint64_t(1) << 34)) return false;
+  if (!key_range_fits(st.min, st.max, uint64_t(1) << 34)) return false;
+  const uint64_t range = key_range(st.min, st.max).n;
   if (mykey->unique_flag == 0) return false;
   bool cached = false;
   {
@@ -838,14 +859,21 @@ static bool bits_map_for(Session *s, const ColPtr &parent_key, const ColPtr &myk
       KERNEL_CHECK();
     }
     // duplicates → not a membership map.  Uniqueness is a property of the
-    // (immutable) key column: read back once, cached on the column
+    // (immutable) key column, but this pass sees only the keys inside the
+    // parent's range: a duplicate it finds settles the flag (0) for good, none
+    // found settles it (1) only when the range covers the column's own
+    // [min, max].  While the flag is unknown every build reads *dup back
     if (mykey->unique_flag < 0) {
       uint32_t d = 0;
       HIP_CHECK(hipMemcpyAsync(&d, dup, 4, hipMemcpyDeviceToHost, s->stream));
       s->sync();
-      mykey->unique_flag = d ? 0 : 1;
+      const ColStats &own = column_stats(s, mykey);
+      if (d)
+        mykey->unique_flag = 0;
+      else if (own.non_null == 0 || (st.min <= own.min && own.max <= st.max))
+        mykey->unique_flag = 1;
+      if (d) return false;
     }
-    if (!mykey->unique_flag) return false;
     std::lock_guard<std::mutex> lk(mykey->mu);
     h.bc = std::make_shared<BitsCache>();
     h.bc->bits = h.vals;
@@ -853,6 +881,7 @@ static bool bits_map_for(Session *s, const ColPtr &parent_key, const ColPtr &myk
     mykey->bits_key[0] = st.min;
     mykey->bits_key[1] = st.max;
   }
+  *was_cached = cached;
   memset(&h.m, 0, sizeof(h.m));
   h.m.kind = MAP_BITS;
   h.m.lo = st.min;
@@ -866,8 +895,8 @@ static HostMap new_map_for(Session *s, const ColPtr &parent_key, int64_t sender_
   memset(&h.m, 0, sizeof(h.m));
   const ColStats &st = column_stats(s, parent_key);
   int64_t prow = parent_key->n;
-  uint64_t range = st.non_null > 0 ? (uint64_t)(st.max - st.min) + 1 : 0;
-  if (st.non_null > 0 && range <= (uint64_t(1) << 28) &&
+  const uint64_t range = st.non_null > 0 ? key_range(st.min, st.max).n : 0;  // saturates when wide
+  if (st.non_null > 0 && key_range_fits(st.min, st.max, uint64_t(1) << 28) &&
       range <= 16 * (uint64_t)std::max<int64_t>(std::max(prow, sender_rows), 1024)) {
     h.m.kind = MAP_DENSE;
     h.m.lo = st.min;
@@ -885,8 +914,8 @@ static HostMap new_map_for(Session *s, const ColPtr &parent_key, int64_t sender_
     h.m.kind = MAP_HASH;
     h.m.mask = cap - 1;
     h.keys = s->alloc(8 * cap);
-    h.vals = s->alloc(8 * cap);
-    HIP_CHECK(hipMemsetAsync(h.vals->p, 0, 8 * cap, s->stream));
+    h.vals = s->alloc(8 * (cap + 1));  // + the slot of the key INT64_MIN
+    HIP_CHECK(hipMemsetAsync(h.vals->p, 0, 8 * (cap + 1), s->stream));
     hipLaunchKernelGGL(k_fill_hash_empty, dim3(grid_for((int64_t)cap, 256)), dim3(256), 0,
                        s->stream, (int64_t *)h.keys->p, cap);
     KERNEL_CHECK();
@@ -896,11 +925,22 @@ static HostMap new_map_for(Session *s, const ColPtr &parent_key, int64_t sender_
   return h;
 }
 
+static const char *kind_token(int kind) {
+  return kind == MAP_ONES ? "ones" : kind == MAP_BITS ? "bits" : kind == MAP_DENSE ? "dense" : "hash";
+}
+
 // Count of the acyclic equi-join described by `g` (no inequalities).
 // Adds the join tree's count to the device counter *d_acc (no host wait).
-static bool tree_count(Session *s, JoinGraph &g, unsigned long long *d_acc) {
+// Appends one token per step to `detail` (host side; capf_session_last_plan_detail):
+// the kind of every message sent, then the root's kernel.
+static bool tree_count(Session *s, JoinGraph &g, unsigned long long *d_acc, std::string &detail) {
   const int L = (int)g.leaves.size();
   if (L == 0) return false;
+  auto token = [&](const std::string &t) {
+    if (!detail.empty() && detail.back() != '|') detail += ' ';
+    detail += t;
+  };
+  for (int i = 0; i < g.pair_joins; ++i) token("pair_join");
   // adjacency; reject cycles / multi-edges / disconnected graphs
   std::vector<std::vector<std::pair<int, int>>> adj(L);  // (neighbour, eq index)
   for (size_t e = 0; e < g.eqs.size(); ++e) {
@@ -937,6 +977,9 @@ static bool tree_count(Session *s, JoinGraph &g, unsigned long long *d_acc) {
       root = r;
     }
   }
+  // a node with more joined tables than a job holds: the joins materialise
+  for (int v = 0; v < L; ++v)
+    if ((int)adj[v].size() - (v == root ? 0 : 1) > MAX_CHILD) return false;
   std::vector<LeafData> data(L);
   for (int i = 0; i < L; ++i) data[i] = leaf_data(g.leaves[i]);
   for (int i = 0; i < L; ++i)
@@ -951,7 +994,6 @@ static bool tree_count(Session *s, JoinGraph &g, unsigned long long *d_acc) {
     for (auto &nb : adj[v]) {
       if (nb.first == parent) continue;
       visit(nb.first, v, nb.second);
-      if (j.nchild >= MAX_CHILD) not_impl("join tree node with too many children");
       const auto &eq = g.eqs[nb.second];
       int mycol = eq.first.leaf == v ? eq.first.col : eq.second.col;
       j.cols[j.nchild] = view_of(data[v].data->cols[mycol]);
@@ -982,6 +1024,7 @@ static bool tree_count(Session *s, JoinGraph &g, unsigned long long *d_acc) {
       }
       j.nchild = keep;
       if (keep == 0) {  // every row counts once
+        token("all_rows");
         if (n > 0) hipLaunchKernelGGL(k_add_u64, dim3(1), dim3(64), 0, s->stream, d_acc, (unsigned long long)n);
         return;
       }
@@ -992,11 +1035,14 @@ static bool tree_count(Session *s, JoinGraph &g, unsigned long long *d_acc) {
       // probes against LDS slices (chain2_partitioned.hip)
       if (keep == 1 && j.child[0].kind == MAP_BITS && msg[child_leaf[0]].bc &&
           bits_count_partitioned(s, c0, n, j.child[0].lo, j.child[0].hi, (const uint32_t *)j.child[0].vals,
-                                 msg[child_leaf[0]].bc->mixed, d_acc))
+                                 msg[child_leaf[0]].bc->mixed, d_acc)) {
+        token("bits_partitioned");
         return;
+      }
       if (keep == 1 && n > 0 && c0.data && !c0.valid && aligned &&
           (j.child[0].kind == MAP_BITS || j.child[0].kind == MAP_ONES)) {
         KernelTimer kt(s, "message_pass", (double)cw * n);
+        token(std::string("root1:") + kind_token(j.child[0].kind) + ":w" + std::to_string(cw));
         auto pick = [&](auto ka) {
           constexpr int KA = decltype(ka)::value;
           return cw == 4 ? k_message_root1<KA, 4> : cw == 3 ? k_message_root1<KA, 3> : k_message_root1<KA, 8>;
@@ -1019,27 +1065,42 @@ static bool tree_count(Session *s, JoinGraph &g, unsigned long long *d_acc) {
         const ColStats &st = column_stats(s, mykey);
         if (st.dense_unique && st.non_null == n) {
           msg[v] = ones_map(st.min, st.max);
+          token("ones");
           return;
         }
       }
       // childless leaf with unique keys: a membership bitmap (no pass, no atomics on counts)
-      if (j.nchild == 0 && bits_map_for(s, data[parent].data->cols[pcol], mykey, msg[v])) return;
+      bool bits_cached = false;
+      if (j.nchild == 0 && bits_map_for(s, data[parent].data->cols[pcol], mykey, msg[v], &bits_cached)) {
+        token(bits_cached ? "bits_cached" : "bits");
+        return;
+      }
       msg[v] = new_map_for(s, data[parent].data->cols[pcol], n);
       // the parent's key column has no value: the empty all-ones map already
       // weighs every key 0 — nothing to add (the map has no storage)
-      if (msg[v].m.kind == MAP_ONES) return;
+      if (msg[v].m.kind == MAP_ONES) {
+        token("empty");
+        return;
+      }
+      token(kind_token(msg[v].m.kind));
       j.cols[j.nchild] = view_of(mykey);
       j.has_parent = 1;
       j.out = msg[v].m;
     }
+    const bool root2 = !j.has_parent && j.nchild == 2 && !j.cols[0].valid && !j.cols[1].valid &&
+                       j.cols[0].data && j.cols[1].data;
+    const bool f32 = root2 && j.cols[0].enc == ENC_FOR32 && j.cols[1].enc == ENC_FOR32;
+    auto simple = [](int k) { return k == MAP_ONES || k == MAP_BITS; };
+    const bool root2_f32 = f32 && simple(j.child[0].kind) && simple(j.child[1].kind);
+    if (!j.has_parent)
+      token(n == 0     ? std::string("no_rows")
+            : root2_f32 ? std::string("root2_f32:") + kind_token(j.child[0].kind) + "," + kind_token(j.child[1].kind)
+            : root2     ? std::string("root2")
+                        : "generic:" + std::to_string(j.nchild));
     if (n == 0) return;
     {
       KernelTimer kt(s, "message_pass", 8.0 * n * (j.nchild + j.has_parent));
-      const bool root2 = !j.has_parent && j.nchild == 2 && !j.cols[0].valid && !j.cols[1].valid &&
-                         j.cols[0].data && j.cols[1].data;
-      const bool f32 = root2 && j.cols[0].enc == ENC_FOR32 && j.cols[1].enc == ENC_FOR32;
-      auto simple = [](int k) { return k == MAP_ONES || k == MAP_BITS; };
-      if (f32 && simple(j.child[0].kind) && simple(j.child[1].kind)) {
+      if (root2_f32) {
         auto kern = j.child[0].kind == MAP_BITS
                         ? (j.child[1].kind == MAP_BITS ? k_message_root2_f32<MAP_BITS, MAP_BITS>
                                                        : k_message_root2_f32<MAP_BITS, MAP_ONES>)
@@ -1078,6 +1139,57 @@ bool column_unique(const NodePtr &node, int col) {
   return idc->unique_flag == 1;
 }
 
+// Leaves A < B of g joined on more than one key pair (an equality of g.eqs and
+// those of `extra`) become ONE leaf: their inner join on all the pairs, a lazy
+// plan node that leaf_data materialises (rows: the 2-cycles of a merged scan
+// and the scan between — far fewer than the joins of the whole pattern).  Its
+// columns are A's, then B's; every other equality is re-addressed.
+static void contract_pair(JoinGraph &g, int A, int B, std::vector<std::pair<ColRef, ColRef>> &extra) {
+  NodePtr l = leaf_plan(g.leaves[A]), r = leaf_plan(g.leaves[B]);
+  auto j = std::make_shared<Node>();
+  j->s = l->s;
+  j->kind = Kind::Join;
+  j->kids = {l, r};
+  j->join_type = CAPF_JOIN_INNER;
+  auto take = [&](std::vector<std::pair<ColRef, ColRef>> &v) {
+    for (auto it = v.begin(); it != v.end();) {
+      const ColRef &x = it->first, &y = it->second;
+      if (x.leaf == A && y.leaf == B)
+        j->join_keys.emplace_back(x.col, y.col);
+      else if (x.leaf == B && y.leaf == A)
+        j->join_keys.emplace_back(y.col, x.col);
+      else {
+        ++it;
+        continue;
+      }
+      it = v.erase(it);
+    }
+  };
+  take(g.eqs);
+  take(extra);
+  for (auto &nm : l->names) j->names.push_back("l." + nm);
+  for (auto &nm : r->names) j->names.push_back("r." + nm);
+  j->types = l->types;
+  j->types.insert(j->types.end(), r->types.begin(), r->types.end());
+  const int nA = (int)l->names.size();
+  g.leaves[A] = Leaf{j, {}, {}};
+  g.leaves.erase(g.leaves.begin() + B);
+  auto remap = [&](ColRef &c) {
+    if (c.leaf == B) {
+      c.leaf = A;
+      c.col += nA;
+    } else if (c.leaf > B) {
+      --c.leaf;
+    }
+  };
+  for (auto *v : {&g.eqs, &extra})
+    for (auto &e : *v) {
+      remap(e.first);
+      remap(e.second);
+    }
+  ++g.pair_joins;
+}
+
 static bool apply_equalities(const JoinGraph &g, const std::vector<int> &subset, JoinGraph &out) {
   const int L = (int)g.leaves.size();
   std::vector<int> rep(L);
@@ -1111,6 +1223,7 @@ static bool apply_equalities(const JoinGraph &g, const std::vector<int> &subset,
   for (auto &t : intra) out.leaves[newid[find(std::get<0>(t))]].col_eqs.emplace_back(std::get<1>(t), std::get<2>(t));
   // re-express equalities; same-leaf equalities become intra-row predicates,
   // parallel edges sharing one side collapse (x=y ∧ x'=y → x=x' intra-row)
+  std::vector<std::pair<ColRef, ColRef>> extra;  // further key pairs of an already joined pair of leaves
   for (auto &e : g.eqs) {
     ColRef a{newid[find(e.first.leaf)], e.first.col};
     ColRef b{newid[find(e.second.leaf)], e.second.col};
@@ -1135,9 +1248,18 @@ static bool apply_equalities(const JoinGraph &g, const std::vector<int> &subset,
         merged = true;
         break;
       }
-      return false;  // genuine two-key join: not a tree
+      // a genuine two-key join of this pair of leaves (the r1 = r3 term of a
+      // directed three-hop chain: merged.t = r2.s AND r2.t = merged.s, the
+      // 2-cycles): no tree over single-column keys — contracted below
+      extra.emplace_back(a, b);
+      merged = true;
+      break;
     }
     if (!merged) out.eqs.emplace_back(a, b);
+  }
+  while (!extra.empty()) {
+    const int A = extra[0].first.leaf, B = extra[0].second.leaf;
+    contract_pair(out, std::min(A, B), std::max(A, B), extra);
   }
   return true;
 }
@@ -1291,8 +1413,8 @@ static bool node_weights(Session *s, const LeafData &ld, int col, NodeWeights &w
     w.ones = true;
     return true;
   }
-  uint64_t range = (uint64_t)(st.max - st.min) + 1;
-  if (range > (uint64_t(1) << 31) || range > 64 * (uint64_t)std::max<int64_t>(c->n, 1024))
+  const uint64_t range = key_range(st.min, st.max).n;  // saturates when wide
+  if (!key_range_fits(st.min, st.max, uint64_t(1) << 31) || range > 64 * (uint64_t)std::max<int64_t>(c->n, 1024))
     return false;
   w.cnt = s->alloc(4 * range);
   HIP_CHECK(hipMemsetAsync(w.cnt->p, 0, 4 * range, s->stream));
@@ -1577,16 +1699,20 @@ bool try_fused_count(const NodePtr &n, int64_t *out) {
   BufPtr slots = s->alloc(8 * (1 << k) + 8);
   HIP_CHECK(hipMemsetAsync(slots->p, 0, 8 * (1 << k) + 8, s->stream));
   unsigned long long *d_slots = (unsigned long long *)slots->p;
-  for (int mask = 0; mask < (1 << k); ++mask)
-    if (!tree_count(s, terms[mask], d_slots + mask)) {
+  std::string detail;  // one token per message and root, terms separated by '|'
+  for (int mask = 0; mask < (1 << k); ++mask) {
+    if (mask) detail += '|';
+    if (!tree_count(s, terms[mask], d_slots + mask, detail)) {
       s->sync();  // kernels of earlier terms may still read their maps
       return false;
     }
+  }
   int64_t *dst = s->async_out ? s->async_out : (int64_t *)(d_slots + (1 << k));
   hipLaunchKernelGGL(k_signed_terms, dim3(1), dim3(64), 0, s->stream,
                      (const unsigned long long *)d_slots, k, dst);
   KERNEL_CHECK();
   s->last_plan = "message_passing";
+  s->last_plan_detail = std::move(detail);
   if (s->async_out) {
     *out = 0;
     return true;

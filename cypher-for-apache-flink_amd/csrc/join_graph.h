@@ -28,6 +28,9 @@ struct JoinGraph {
   // literal columns met on the way (withColumns of literals): ColRef{-2, k}
   // refers to lits[k]
   std::vector<Program> lits;
+  // pairs of leaves joined on several keys, replaced by one leaf each: their
+  // materialised inner join (fused_count.hip contract_pair)
+  int pair_joins = 0;
 };
 
 struct LeafData {

@@ -1347,6 +1347,7 @@ capf_status capf_session_reset_profile(capf_session *cs) {
   cs->impl.resolve_profile();
   cs->impl.profile.clear();
   cs->impl.last_plan = "none";
+  cs->impl.last_plan_detail.clear();
   CAPF_API_END
 }
 
@@ -1375,6 +1376,10 @@ capf_status capf_session_profile_entry(capf_session *cs, int32_t i, const char *
 
 const char *capf_session_last_plan(capf_session *cs) {
   return cs ? cs->impl.last_plan.c_str() : "";
+}
+
+const char *capf_session_last_plan_detail(capf_session *cs) {
+  return cs ? cs->impl.last_plan_detail.c_str() : "";
 }
 
 capf_status capf_string_intern(capf_session *cs, const char *str, int64_t *code) {

@@ -297,6 +297,11 @@ class GpuSession:
     def last_plan(self):
         return _lib.load().capf_session_last_plan(self._h).decode()
 
+    def last_plan_detail(self):
+        """The messages and the root kernel of the last "message_passing" count,
+        one token per step, terms separated by '|' ("" until one runs)."""
+        return _lib.load().capf_session_last_plan_detail(self._h).decode()
+
     def sync(self):
         _lib.call("capf_session_sync", self._h)
 

@@ -295,6 +295,8 @@ capf_status capf_session_profile_entry(capf_session *s, int32_t i, const char **
  * (lower bound >= 2: trail enumeration), "fused_var_length_undirected" (undirected
  * pattern: step enumeration); "none" until one runs) */
 const char *capf_session_last_plan(capf_session *s);
+/* the messages and root kernel of the last "message_passing" count (DESIGN.md "Plan detail"); "" until one runs */
+const char *capf_session_last_plan_detail(capf_session *s);
 
 /* String dictionary for CAPF_TYPE_STRING columns. */
 capf_status capf_string_intern(capf_session *s, const char *str, int64_t *code);

@@ -225,6 +225,10 @@ JNI(jstring, sessionLastPlan)(JNIEnv *env, jobject, jlong s) {
   const char *p = capf_session_last_plan(S(s));
   return env->NewStringUTF(p ? p : "");
 }
+JNI(jstring, sessionLastPlanDetail)(JNIEnv *env, jobject, jlong s) {
+  const char *p = capf_session_last_plan_detail(S(s));
+  return env->NewStringUTF(p ? p : "");
+}
 
 // CTString dictionary
 JNI(jlong, stringIntern)(JNIEnv *env, jobject, jlong s, jstring str) {

@@ -119,6 +119,7 @@ object Native {
   @native def sessionProfileCount(session: Long): Int
   @native def sessionProfileEntry(session: Long, i: Int, launchesOut: Array[Long], msBytesOut: Array[Double]): String
   @native def sessionLastPlan(session: Long): String
+  @native def sessionLastPlanDetail(session: Long): String
   @native def stringIntern(session: Long, s: String): Long
   @native def stringLookup(session: Long, code: Long): String
   @native def stringDigest(session: Long, out: Array[Long]): Unit
