@@ -16,10 +16,10 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/capf_gpu.h"
+#include "string_dict.h"
 
 namespace capf {
 
@@ -410,50 +410,8 @@ struct Session {
   // which messages and root kernel the last message-passing count used
   // (fused_count.hip tree_count; DESIGN.md "Plan detail"); "" until one runs
   std::string last_plan_detail;
-  // string dictionary
-  std::mutex str_mu;
-  std::vector<std::string> strings;
-  std::unordered_map<std::string, int64_t> string_codes;
-  // device table of the strings' lengths (CAPF_OP_STR_LEN), grown on demand
-  BufPtr d_str_len;
-  size_t d_str_len_n = 0;
-  // device table of the strings as booleans (CAPF_OP_TO_BOOLEAN): 0 false,
-  // 1 true, 2 neither (NULL)
-  BufPtr d_str_bool;
-  size_t d_str_bool_n = 0;
-  // device table of the strings' sort ranks (CAPF_OP_STR_RANK) and its inverse
-  BufPtr d_str_rank, d_str_order;
-  size_t d_str_rank_n = 0;
-  // device table of the strings as numbers (CAPF_OP_STR_TO_NUM)
-  BufPtr d_str_num;
-  size_t d_str_num_n = 0;
-  // device string heap (CAPF_OP_STR_MATCH): int64 offsets [n + 1] and the
-  // strings' bytes back to back, appended to as the dictionary grows
-  // (capacities in offsets / bytes, geometric)
-  BufPtr d_heap_off, d_heap_bytes;
-  size_t d_heap_n = 0, d_heap_off_cap = 0;
-  int64_t d_heap_nbytes = 0, d_heap_bytes_cap = 0;
-  // device tables of CAPF_OP_STR_MATCH with a literal pattern: one uint8
-  // (0 / 1) per dictionary code, per (kind, pattern code); oldest first, at
-  // most STR_MATCH_TABLES kept
-  struct StrMatchTable {
-    int32_t kind;
-    int64_t pattern;
-    BufPtr buf;
-    size_t n, cap;  // codes covered, capacity
-  };
-  std::mutex match_mu;
-  std::vector<StrMatchTable> match_tables;
-  // device hash index of the dictionary (string_fn.hip): an open-addressed
-  // table of codes (−1 empty, `slots` a power of two, at most half full) keyed
-  // by the 64-bit hash of each string's bytes, and those hashes by code;
-  // extended over the codes interned since, rebuilt when it passes half full
-  struct StrIndex {
-    BufPtr tab, hashes;
-    size_t n = 0, slots = 0, hash_cap = 0;  // codes covered, table slots, hashes allocated
-  };
-  std::mutex index_mu;
-  StrIndex str_index;
+  // string dictionary: the strings and every device table derived from them (string_dict.h)
+  StringDict dict{this};
   // small device scratch for scalar results
   int64_t *d_scalars = nullptr;  // 64 slots
   int64_t *h_scalars = nullptr;  // pinned mirror
@@ -619,35 +577,12 @@ ColPtr const_column(Session *s, const Column &c, int64_t m);
 ColPtr encode_column(Session *s, const ColPtr &c, int width = 4);
 ColPtr decode_column(Session *s, const ColPtr &c);
 
-// Device table of the session's string lengths by code (UTF-16 units), for
-// CAPF_OP_STR_LEN; *n = strings covered.
-const int64_t *string_length_table(Session *s, size_t *n);
-// Device table of the session's strings parsed as booleans (CAPF_OP_TO_BOOLEAN).
-const uint8_t *string_bool_table(Session *s, size_t *n);
-// Device table of each string's rank in UTF-16 code-unit order
-// (CAPF_OP_STR_RANK, Java String.compareTo); *n = strings covered.
-const int64_t *string_rank_table(Session *s, size_t *n);
-// Its inverse: the code of the string of each rank.
-const int64_t *string_order_table(Session *s, size_t *n);
 // STRING column of the codes of an INTEGER column of ranks (NULLs kept).
 ColPtr ranks_to_codes(Session *s, const ColPtr &ranks);
-// Device table of the session's strings parsed as numbers (CAPF_OP_STR_TO_NUM):
-// [double n][int64 n][uint8 flags n] (bit 0: a DOUBLE, bit 1: an INTEGER).
-const void *string_num_table(Session *s, size_t *n);
-// The session's strings on the device (CAPF_OP_STR_MATCH): int64 offsets
-// [n + 1] and the UTF-8 / WTF-8 bytes back to back, no terminators.  Only the
-// strings interned since the last call are uploaded.  The bytes buffer is
-// padded so that aligned 4-byte words covering any string may be read.
-struct StringHeap {
-  BufPtr off, bytes;
-  int64_t nbytes;
-};
-StringHeap string_heap(Session *s, size_t *n);
 // Device uint8 table (0 false, 1 true) of `subject <kind> pattern` per
 // dictionary code for one pattern (strings.hip); cached per (kind, pattern)
 // and extended over the codes interned since.  kind: 0 STARTS WITH, 1 ENDS
 // WITH, 2 CONTAINS.
-constexpr size_t STR_MATCH_TABLES = 16;  // cached tables per session
 BufPtr string_match_table(Session *s, int kind, int64_t pattern_code, size_t *n);
 // The path of a literal pattern over `nrows` rows: true = the table above
 // (the strings it does not cover yet are at most the rows), false = row by
@@ -655,16 +590,6 @@ BufPtr string_match_table(Session *s, int kind, int64_t pattern_code, size_t *n)
 bool string_match_by_table(Session *s, int kind, int64_t pattern_code, int64_t nrows);
 // Bytes from which a string goes to a wave instead of a thread (CAPF_STR_LONG, default 256).
 int64_t string_long_threshold();
-// The strings a device step made against a snapshot of n0 dictionary strings
-// (heap end `base`), as codes n0, n0 + 1, …: n_new end offsets (absolute, from
-// `base` on) and nb bytes, on the device and copied to the host.  While the
-// dictionary still holds n0 strings they are appended to the heap device to
-// device and to the host dictionary; when another thread interned meanwhile,
-// each is resolved through the host map instead (the heap catches up at its
-// next use).  codes[r] = the code of new string r.
-void string_heap_append(Session *s, size_t n0, int64_t base, const int64_t *d_offs, const uint8_t *d_bytes,
-                        const int64_t *h_offs, const char *h_bytes, int64_t n_new, int64_t nb,
-                        std::vector<int64_t> &codes);
 // A string function (CAPF_STR_FN_*) of n dictionary strings — the codes src[i]
 // (−1 NULL), or c0 + i when src is null — evaluated on the heap and interned
 // on the device (string_fn.hip): out[i] (host) = the result's code, −1 NULL,

@@ -600,8 +600,8 @@ __global__ void k_rank_codes(ColView r, const int64_t *order, int64_t n, int64_t
 
 ColPtr ranks_to_codes(Session *s, const ColPtr &ranks) {
   force(ranks);
-  size_t ns = 0;
-  const int64_t *order = string_order_table(s, &ns);
+  const StringDict::Table rk = s->dict.table(StringDict::RANK);  // held past the launch
+  const int64_t *order = (const int64_t *)rk.buf->p + rk.rows();
   const int64_t n = ranks->n;
   ColPtr o = make_column(s, Type::String, n, true);
   if (n > 0) {
@@ -1400,40 +1400,29 @@ static DeviceProgram upload_program(Session *s, const Program &p,
     }
   }
   std::vector<Instr> code = p.code;
-  for (auto &in : code)
-    if (in.op == OP_STR_LEN) {  // the session's string lengths as one more column view
-      size_t nstr = 0;
-      const int64_t *len = string_length_table(s, &nstr);
-      in.i = (int64_t)views.size();
-      views.push_back(ColView{len, nullptr, (int32_t)Type::Int64, ENC_PLAIN, 0});
-      for (auto &x : code)
-        if (x.op == OP_STR_LEN) x.i = in.i;
-      break;
-    }
-  for (auto &in : code)
-    if (in.op == OP_STR_RANK) {  // the session's string sort ranks as one more column view
-      size_t nstr = 0;
-      const int64_t *rk = string_rank_table(s, &nstr);
-      in.i = (int64_t)views.size();
-      views.push_back(ColView{rk, nullptr, (int32_t)Type::Int64, ENC_PLAIN, 0});
-      dp.keep.push_back(s->d_str_rank);
-      for (auto &x : code)
-        if (x.op == OP_STR_RANK) x.i = in.i;
-      break;
-    }
-  for (auto &in : code)
-    if (in.op == OP_STR_TO_NUM) {  // the session's strings as numbers, one more view
-      size_t nstr = 0;
-      const void *tn = string_num_table(s, &nstr);
-      const int64_t vi = (int64_t)views.size();
-      views.push_back(ColView{tn, nullptr, (int32_t)Type::Float64, ENC_PLAIN, (int64_t)std::max<size_t>(nstr, 1)});
-      for (auto &x : code)
-        if (x.op == OP_STR_TO_NUM) {
-          x.f = (double)x.i;  // 1 DOUBLE, 0 INTEGER
-          x.i = vi;
-        }
-      break;
-    }
+  // A dictionary buffer (string_dict.h) as one more view, kept by the program:
+  // the dictionary replaces a table when it has grown, on any thread.
+  auto dict_view = [&](const BufPtr &b, Type t, int64_t base) {
+    views.push_back(ColView{b->p, nullptr, (int32_t)t, ENC_PLAIN, base});
+    dp.keep.push_back(b);
+    return (int64_t)views.size() - 1;
+  };
+  // Every instruction of `op` reads dictionary table `id` through one view, its
+  // index in i (i_to_f: the instruction's own i moves to f first); sized: the
+  // table's rows in the view's `base`.
+  auto table_op = [&](int32_t op, StringDict::TableId id, Type t, bool sized, bool i_to_f) {
+    if (std::none_of(code.begin(), code.end(), [&](const Instr &x) { return x.op == op; })) return;
+    const StringDict::Table tb = s->dict.table(id);
+    const int64_t vi = dict_view(tb.buf, t, sized ? (int64_t)tb.rows() : 0);
+    for (auto &x : code)
+      if (x.op == op) {
+        if (i_to_f) x.f = (double)x.i;
+        x.i = vi;
+      }
+  };
+  table_op(OP_STR_LEN, StringDict::LEN, Type::Int64, false, false);
+  table_op(OP_STR_RANK, StringDict::RANK, Type::Int64, false, false);
+  table_op(OP_STR_TO_NUM, StringDict::NUM, Type::Float64, true, true);  // f: 1 DOUBLE, 0 INTEGER
   for (auto &in : code)
     if (in.op == OP_LIST_INDEX || in.op == OP_IN_LIST) {  // the element column of the list as one more view (index in f)
       int idx = -1;
@@ -1449,16 +1438,7 @@ static DeviceProgram upload_program(Session *s, const Program &p,
       in.f = (double)views.size();
       views.push_back(view_of(c->child));
     }
-  for (auto &in : code)
-    if (in.op == OP_TO_BOOLEAN) {  // the session's strings as booleans, one more view
-      size_t nstr = 0;
-      const uint8_t *tb = string_bool_table(s, &nstr);
-      in.i = (int64_t)views.size();
-      views.push_back(ColView{tb, nullptr, (int32_t)Type::Bool, ENC_PLAIN, 0});
-      for (auto &x : code)
-        if (x.op == OP_TO_BOOLEAN) x.i = in.i;
-      break;
-    }
+  table_op(OP_TO_BOOLEAN, StringDict::BOOL, Type::Bool, false, false);
   // STARTS WITH / ENDS WITH / CONTAINS: a literal pattern (the instruction
   // before is its LIT_STRING) reads its per-dictionary-code table as one more
   // view when that examines no more strings than the input has rows
@@ -1475,20 +1455,14 @@ static DeviceProgram upload_program(Session *s, const Program &p,
     if (lit && string_match_by_table(s, (int)kind, code[k - 1].i, d.nrows)) {
       size_t nstr = 0;
       BufPtr t = string_match_table(s, (int)kind, code[k - 1].i, &nstr);
-      in.i = 4 * (int64_t)views.size() + kind;
+      in.i = 4 * dict_view(t, Type::Bool, (int64_t)nstr) + kind;
       in.f = 1.0;
-      views.push_back(ColView{t->p, nullptr, (int32_t)Type::Bool, ENC_PLAIN, (int64_t)nstr});
-      dp.keep.push_back(t);
       continue;
     }
     if (heap_view < 0) {
-      size_t nstr = 0;
-      const StringHeap h = string_heap(s, &nstr);
-      heap_view = (int64_t)views.size();
-      views.push_back(ColView{h.off->p, nullptr, (int32_t)Type::Int64, ENC_PLAIN, (int64_t)nstr});
-      views.push_back(ColView{h.bytes->p, nullptr, (int32_t)Type::Int64, ENC_PLAIN, h.nbytes});
-      dp.keep.push_back(h.off);
-      dp.keep.push_back(h.bytes);
+      const StringHeap h = s->dict.heap();
+      heap_view = dict_view(h.off, Type::Int64, (int64_t)h.n);
+      dict_view(h.bytes, Type::Int64, h.nbytes);
     }
     in.i = 4 * heap_view + kind;
     in.f = 0.0;

@@ -784,285 +784,6 @@ int64_t node_size(const NodePtr &n) {
   if (try_fused_count(n, &cnt)) return cnt;
   return materialize(n)->nrows;
 }
-
-// Java String.length of a UTF-8 string: UTF-16 code units (one per code point,
-// two above U+FFFF)
-static int64_t utf16_length(const std::string &u) {
-  int64_t n = 0;
-  for (size_t i = 0; i < u.size(); ++i) {
-    const unsigned char c = (unsigned char)u[i];
-    if ((c & 0xC0) == 0x80) continue;  // continuation byte
-    n += c >= 0xF0 ? 2 : 1;
-  }
-  return n;
-}
-
-const int64_t *string_length_table(Session *s, size_t *n) {
-  std::lock_guard<std::mutex> lk(s->str_mu);
-  if (s->d_str_len_n != s->strings.size() || !s->d_str_len) {
-    std::vector<int64_t> len(std::max<size_t>(s->strings.size(), 1), 0);
-    for (size_t i = 0; i < s->strings.size(); ++i) len[i] = utf16_length(s->strings[i]);
-    s->d_str_len = s->alloc(8 * len.size());
-    HIP_CHECK(hipMemcpyAsync(s->d_str_len->p, len.data(), 8 * len.size(), hipMemcpyHostToDevice, s->stream));
-    s->sync();  // the pageable source
-    s->d_str_len_n = s->strings.size();
-  }
-  *n = s->d_str_len_n;
-  return (const int64_t *)s->d_str_len->p;
-}
-
-// Flink's CAST(string AS BOOLEAN) (FlinkSQLExprMapper.scala:185): 'true' /
-// 'false' in any case, surrounding blanks ignored; anything else is NULL
-static uint8_t parse_bool(const std::string &u) {
-  size_t b = 0, e = u.size();
-  while (b < e && (unsigned char)u[b] <= ' ') ++b;
-  while (e > b && (unsigned char)u[e - 1] <= ' ') --e;
-  std::string t = u.substr(b, e - b);
-  for (auto &ch : t) ch = (char)std::tolower((unsigned char)ch);
-  return t == "true" ? 1 : t == "false" ? 0 : 2;
-}
-
-const uint8_t *string_bool_table(Session *s, size_t *n) {
-  std::lock_guard<std::mutex> lk(s->str_mu);
-  if (s->d_str_bool_n != s->strings.size() || !s->d_str_bool) {
-    std::vector<uint8_t> v(std::max<size_t>(s->strings.size(), 1), 2);
-    for (size_t i = 0; i < s->strings.size(); ++i) v[i] = parse_bool(s->strings[i]);
-    s->d_str_bool = s->alloc(v.size());
-    HIP_CHECK(hipMemcpyAsync(s->d_str_bool->p, v.data(), v.size(), hipMemcpyHostToDevice, s->stream));
-    s->sync();  // the pageable source
-    s->d_str_bool_n = s->strings.size();
-  }
-  *n = s->d_str_bool_n;
-  return (const uint8_t *)s->d_str_bool->p;
-}
-// CAST(string AS DOUBLE): java.lang.Double.valueOf after String.trim —
-// [+-] (NaN | Infinity | digits[.digits] | .digits)([eE][+-]digits)? [fFdD]?
-static bool parse_java_double(const std::string &u, double *out) {
-  size_t b = 0, e = u.size();
-  while (b < e && (unsigned char)u[b] <= ' ') ++b;
-  while (e > b && (unsigned char)u[e - 1] <= ' ') --e;
-  std::string t = u.substr(b, e - b);
-  if (t.empty()) return false;
-  size_t i = 0;
-  if (t[i] == '+' || t[i] == '-') ++i;
-  const std::string rest = t.substr(i);
-  if (rest == "NaN" || rest == "Infinity") {
-    *out = rest == "NaN" ? std::nan("") : (t[0] == '-' ? -HUGE_VAL : HUGE_VAL);
-    return true;
-  }
-  size_t d0 = i, nd = 0;
-  while (i < t.size() && isdigit((unsigned char)t[i])) ++i, ++nd;
-  if (i < t.size() && t[i] == '.') {
-    ++i;
-    while (i < t.size() && isdigit((unsigned char)t[i])) ++i, ++nd;
-  }
-  if (nd == 0) return false;
-  if (i < t.size() && (t[i] == 'e' || t[i] == 'E')) {
-    ++i;
-    if (i < t.size() && (t[i] == '+' || t[i] == '-')) ++i;
-    size_t ne = 0;
-    while (i < t.size() && isdigit((unsigned char)t[i])) ++i, ++ne;
-    if (ne == 0) return false;
-  }
-  const size_t num_end = i;
-  if (i < t.size() && strchr("fFdD", t[i])) ++i;
-  if (i != t.size()) return false;
-  (void)d0;
-  *out = strtod(t.substr(0, num_end).c_str(), nullptr);
-  return true;
-}
-
-// CAST(string AS INT), the semantics the reference expectations pin
-// (FunctionTests.scala:1101-1152): a decimal integer after trim, a fractional
-// part truncated ('82.9' -> 82), within 32 bits; anything else NULL
-static bool parse_int32(const std::string &u, int64_t *out) {
-  size_t b = 0, e = u.size();
-  while (b < e && (unsigned char)u[b] <= ' ') ++b;
-  while (e > b && (unsigned char)u[e - 1] <= ' ') --e;
-  size_t i = b;
-  bool neg = false;
-  if (i < e && (u[i] == '+' || u[i] == '-')) neg = u[i++] == '-';
-  int64_t v = 0;
-  size_t nd = 0;
-  while (i < e && isdigit((unsigned char)u[i])) {
-    v = v * 10 + (u[i++] - '0');
-    if (v > (int64_t)1 << 32) v = (int64_t)1 << 32;  // saturate: out of range below
-    ++nd;
-  }
-  if (nd == 0) return false;
-  if (i < e && u[i] == '.') {
-    ++i;
-    while (i < e && isdigit((unsigned char)u[i])) ++i;
-  }
-  if (i != e) return false;
-  if (neg) v = -v;
-  if (v < -2147483648LL || v > 2147483647LL) return false;
-  *out = v;
-  return true;
-}
-
-// Java String.compareTo order: UTF-16 code units.  On UTF-8 bytes that is
-// code-point order except that a supplementary character (4 bytes, a
-// surrogate pair D800-DBFF first) sorts below U+E000-U+FFFF (3 bytes EE-EF).
-static int utf16_cmp(const std::string &a, const std::string &b) {
-  auto key = [](const std::string &u, size_t &i) -> uint32_t {  // next code unit class
-    const unsigned char c = (unsigned char)u[i];
-    size_t len = c < 0x80 ? 1 : c < 0xE0 ? 2 : c < 0xF0 ? 3 : 4;
-    uint32_t cp = c < 0x80 ? c : c < 0xE0 ? c & 0x1F : c < 0xF0 ? c & 0x0F : c & 0x07;
-    for (size_t k = 1; k < len && i + k < u.size(); ++k) cp = cp << 6 | ((unsigned char)u[i + k] & 0x3F);
-    i += len;
-    return cp >= 0x10000 ? 0xD800 + ((cp - 0x10000) >> 10) : cp;  // the high surrogate
-  };
-  size_t i = 0, j = 0;
-  while (i < a.size() && j < b.size()) {
-    const size_t i0 = i, j0 = j;
-    const uint32_t x = key(a, i), y = key(b, j);
-    if (x != y) return x < y ? -1 : 1;
-    if (x >= 0xD800 && x < 0xDC00) {  // equal high surrogates: compare the low ones
-      std::string ca = a.substr(i0, i - i0), cb = b.substr(j0, j - j0);
-      if (ca != cb) return ca < cb ? -1 : 1;  // same lead: byte order = low-surrogate order
-    }
-  }
-  return i < a.size() ? 1 : (j < b.size() ? -1 : 0);
-}
-
-const int64_t *string_rank_table(Session *s, size_t *n) {
-  std::lock_guard<std::mutex> lk(s->str_mu);
-  if (s->d_str_rank_n != s->strings.size() || !s->d_str_rank) {
-    const size_t m = s->strings.size();
-    std::vector<int64_t> order(m), rank(std::max<size_t>(m, 1), 0);
-    for (size_t i = 0; i < m; ++i) order[i] = (int64_t)i;
-    std::sort(order.begin(), order.end(),
-              [&](int64_t x, int64_t y) { return utf16_cmp(s->strings[x], s->strings[y]) < 0; });
-    for (size_t r = 0; r < m; ++r) rank[(size_t)order[r]] = (int64_t)r;
-    s->d_str_rank = s->alloc(8 * rank.size());
-    HIP_CHECK(hipMemcpyAsync(s->d_str_rank->p, rank.data(), 8 * rank.size(), hipMemcpyHostToDevice, s->stream));
-    if (order.empty()) order.push_back(0);
-    s->d_str_order = s->alloc(8 * order.size());
-    HIP_CHECK(hipMemcpyAsync(s->d_str_order->p, order.data(), 8 * order.size(), hipMemcpyHostToDevice, s->stream));
-    s->sync();  // the pageable sources
-    s->d_str_rank_n = m;
-  }
-  *n = s->d_str_rank_n;
-  return (const int64_t *)s->d_str_rank->p;
-}
-
-const int64_t *string_order_table(Session *s, size_t *n) {
-  string_rank_table(s, n);
-  std::lock_guard<std::mutex> lk(s->str_mu);
-  return (const int64_t *)s->d_str_order->p;
-}
-
-// Heap buffers keep HEAP_PAD bytes past the last string: the matching kernels
-// read the aligned 4-byte words that cover a string, and CONTAINS's window one
-// word ahead.
-constexpr int64_t HEAP_PAD = 16;
-
-// Room for m strings of `end` bytes in all (str_mu held): geometric
-// capacities; a grown buffer takes its content device to device.
-static void heap_reserve(Session *s, size_t m, int64_t end) {
-  const size_t have = s->d_heap_off ? s->d_heap_n : 0;
-  if (m + 1 > s->d_heap_off_cap) {
-    const size_t cap = std::max<size_t>(2 * s->d_heap_off_cap, std::max<size_t>(m + 1, 1024));
-    BufPtr nb = s->alloc(8 * cap);
-    if (s->d_heap_off)
-      HIP_CHECK(hipMemcpyAsync(nb->p, s->d_heap_off->p, 8 * (have + 1), hipMemcpyDeviceToDevice, s->stream));
-    s->d_heap_off = nb;
-    s->d_heap_off_cap = cap;
-  }
-  if (end + HEAP_PAD > s->d_heap_bytes_cap || !s->d_heap_bytes) {
-    const int64_t cap = std::max<int64_t>(2 * s->d_heap_bytes_cap, std::max<int64_t>(end + HEAP_PAD, 1 << 16));
-    BufPtr nb = s->alloc((size_t)cap);
-    if (s->d_heap_bytes && s->d_heap_nbytes > 0)
-      HIP_CHECK(hipMemcpyAsync(nb->p, s->d_heap_bytes->p, (size_t)s->d_heap_nbytes, hipMemcpyDeviceToDevice,
-                               s->stream));
-    s->d_heap_bytes = nb;
-    s->d_heap_bytes_cap = cap;
-  }
-}
-
-void string_heap_append(Session *s, size_t n0, int64_t base, const int64_t *d_offs, const uint8_t *d_bytes,
-                        const int64_t *h_offs, const char *h_bytes, int64_t n_new, int64_t nb,
-                        std::vector<int64_t> &codes) {
-  codes.resize((size_t)n_new);
-  std::lock_guard<std::mutex> lk(s->str_mu);
-  const bool same = s->strings.size() == n0 && s->d_heap_off && s->d_heap_n == n0 && s->d_heap_nbytes == base;
-  if (same) {  // codes n0.. in order; the heap grows device to device
-    heap_reserve(s, n0 + (size_t)n_new, base + nb);
-    HIP_CHECK(hipMemcpyAsync((int64_t *)s->d_heap_off->p + n0 + 1, d_offs, 8 * (size_t)n_new,
-                             hipMemcpyDeviceToDevice, s->stream));
-    if (nb > 0)
-      HIP_CHECK(hipMemcpyAsync((uint8_t *)s->d_heap_bytes->p + base, d_bytes, (size_t)nb, hipMemcpyDeviceToDevice,
-                               s->stream));
-    s->d_heap_n = n0 + (size_t)n_new;
-    s->d_heap_nbytes = base + nb;
-  }
-  int64_t b = base;
-  for (int64_t r = 0; r < n_new; ++r) {
-    std::string str(h_bytes + (b - base), (size_t)(h_offs[r] - b));
-    b = h_offs[r];
-    auto it = same ? s->string_codes.end() : s->string_codes.find(str);
-    if (it != s->string_codes.end()) {
-      codes[(size_t)r] = it->second;
-      continue;
-    }
-    codes[(size_t)r] = (int64_t)s->strings.size();
-    s->string_codes.emplace(str, codes[(size_t)r]);
-    s->strings.push_back(std::move(str));
-  }
-}
-
-StringHeap string_heap(Session *s, size_t *n) {
-  std::lock_guard<std::mutex> lk(s->str_mu);
-  const size_t m = s->strings.size(), have = s->d_heap_off ? s->d_heap_n : 0;
-  if (m > have || !s->d_heap_off) {
-    // the new strings' offsets (and offset 0 the first time) and bytes
-    std::vector<int64_t> off;
-    std::string bytes;
-    if (!s->d_heap_off) off.push_back(0);
-    int64_t end = s->d_heap_off ? s->d_heap_nbytes : 0;
-    for (size_t i = have; i < m; ++i) {
-      bytes += s->strings[i];
-      end += (int64_t)s->strings[i].size();
-      off.push_back(end);
-    }
-    heap_reserve(s, m, end);
-    const size_t first = m + 1 - off.size();  // index of the first offset uploaded
-    HIP_CHECK(hipMemcpyAsync((int64_t *)s->d_heap_off->p + first, off.data(), 8 * off.size(), hipMemcpyHostToDevice,
-                             s->stream));
-    if (!bytes.empty())
-      HIP_CHECK(hipMemcpyAsync((uint8_t *)s->d_heap_bytes->p + (end - (int64_t)bytes.size()), bytes.data(),
-                               bytes.size(), hipMemcpyHostToDevice, s->stream));
-    s->sync();  // the pageable sources
-    s->d_heap_n = m;
-    s->d_heap_nbytes = end;
-  }
-  *n = s->d_heap_n;
-  return StringHeap{s->d_heap_off, s->d_heap_bytes, s->d_heap_nbytes};
-}
-
-const void *string_num_table(Session *s, size_t *n) {
-  std::lock_guard<std::mutex> lk(s->str_mu);
-  if (s->d_str_num_n != s->strings.size() || !s->d_str_num) {
-    const size_t m = std::max<size_t>(s->strings.size(), 1);
-    std::vector<uint8_t> buf(m * 17, 0);
-    double *f = (double *)buf.data();
-    int64_t *iv = (int64_t *)(buf.data() + 8 * m);
-    uint8_t *fl = buf.data() + 16 * m;
-    for (size_t i = 0; i < s->strings.size(); ++i) {
-      double d = 0;
-      int64_t v = 0;
-      if (parse_java_double(s->strings[i], &d)) f[i] = d, fl[i] |= 1;
-      if (parse_int32(s->strings[i], &v)) iv[i] = v, fl[i] |= 2;
-    }
-    s->d_str_num = s->alloc(buf.size());
-    HIP_CHECK(hipMemcpyAsync(s->d_str_num->p, buf.data(), buf.size(), hipMemcpyHostToDevice, s->stream));
-    s->sync();  // the pageable source
-    s->d_str_num_n = s->strings.size();
-  }
-  *n = s->d_str_num_n;
-  return s->d_str_num->p;
-}
 }  // namespace capf
 
 // ===================================================================== C-ABI
@@ -1387,17 +1108,7 @@ capf_status capf_string_intern(capf_session *cs, const char *str, int64_t *code)
   need(cs, "session");
   need(str, "str");
   need(code, "code");
-  Session &s = cs->impl;
-  std::lock_guard<std::mutex> g(s.str_mu);
-  auto it = s.string_codes.find(str);
-  if (it != s.string_codes.end()) {
-    *code = it->second;
-  } else {
-    int64_t c = (int64_t)s.strings.size();
-    s.strings.emplace_back(str);
-    s.string_codes.emplace(str, c);
-    *code = c;
-  }
+  *code = cs->impl.dict.intern(str);
   CAPF_API_END
 }
 
@@ -1405,10 +1116,7 @@ capf_status capf_string_lookup(capf_session *cs, int64_t code, const char **str)
   CAPF_API_BEGIN
   need(cs, "session");
   need(str, "str");
-  Session &s = cs->impl;
-  std::lock_guard<std::mutex> g(s.str_mu);
-  if (code < 0 || code >= (int64_t)s.strings.size()) illegal("unknown string code");
-  *str = s.strings[code].c_str();
+  *str = cs->impl.dict.lookup(code);
   CAPF_API_END
 }
 
@@ -1417,15 +1125,7 @@ capf_status capf_string_digest(capf_session *cs, int64_t *count, uint64_t *diges
   need(cs, "session");
   need(count, "count");
   need(digest, "digest");
-  Session &s = cs->impl;
-  std::lock_guard<std::mutex> g(s.str_mu);
-  uint64_t h = 1469598103934665603ull;
-  for (const std::string &str : s.strings) {
-    for (unsigned char ch : str) h = (h ^ ch) * 1099511628211ull;
-    h = (h ^ 0xffu) * 1099511628211ull;  // separator: ("ab","c") != ("a","bc")
-  }
-  *count = (int64_t)s.strings.size();
-  *digest = h;
+  cs->impl.dict.digest(count, digest);
   CAPF_API_END
 }
 
@@ -2855,9 +2555,7 @@ capf_status capf_table_show(capf_table *t, int32_t rows) {
       } else if (ty == Type::List) {
         printf("[%lld values]", (long long)vals[i][r]);
       } else if (ty == Type::String) {
-        std::lock_guard<std::mutex> g(s->str_mu);
-        printf("'%s'", vals[i][r] >= 0 && vals[i][r] < (int64_t)s->strings.size()
-                           ? s->strings[vals[i][r]].c_str() : "?");
+        printf("'%s'", s->dict.lookup(vals[i][r], "?"));
       } else {
         printf("%lld", (long long)vals[i][r]);
       }

@@ -5,7 +5,7 @@
 // Strings start at any byte, so nothing here loads a string's bytes one by
 // one or through an unaligned pointer: a string is read as the aligned 4-byte
 // words that cover it, shifted into place.  The heap's buffer is 16-byte
-// aligned and padded past its last string (runtime.cpp string_heap), so the
+// aligned and padded past its last string (string_dict.h StringHeap), so the
 // covering words — and CONTAINS's one word of look-ahead — are always inside
 // it; bytes past a string's end are masked off before they are compared.
 #pragma once

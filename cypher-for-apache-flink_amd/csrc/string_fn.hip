@@ -1,6 +1,6 @@
 // string_fn.hip — toUpper / toLower / trim / lTrim / rTrim / substring /
 // replace / s + 'lit' / 'lit' + s with literal arguments, evaluated on the
-// device string heap (runtime.cpp string_heap) and interned there
+// device string heap (string_dict.h heap()) and interned there
 // (capf_string_fn_codes).
 //
 // The input is a worklist of n source codes: a range of the dictionary or a
@@ -21,7 +21,7 @@
 // result of at least L bytes is copied by one wave likewise.  replace walks
 // its subject sequentially, so a long subject is the host's.
 //
-// Interning: a hash index of the dictionary (Session::StrIndex: open-addressed
+// Interning: a hash index of the dictionary (StringDict::Index: open-addressed
 // table of codes keyed by a 64-bit hash of the bytes, at most half full) is
 // probed with each result, a hit confirmed by comparing bytes.  Results not
 // found are grouped among themselves in a scratch table of worklist
@@ -521,25 +521,15 @@ constexpr size_t IDX_MIN_SLOTS = 1 << 12;
 
 // The index over the heap's n strings (index_mu held).
 static void ensure_index(Session *s, const StringHeap &h, size_t n) {
-  Session::StrIndex &ix = s->str_index;
+  StringDict::Index &ix = s->dict.index;
   if (n <= ix.n && ix.tab) return;
   const int64_t *off = (const int64_t *)h.off->p;
   const uint8_t *bytes = (const uint8_t *)h.bytes->p;
-  if (n > ix.hash_cap) {  // geometric; the hashes so far move device to device
-    const size_t cap = std::max<size_t>(2 * ix.hash_cap, std::max<size_t>(n, 4096));
-    BufPtr nb = s->alloc(8 * cap);
-    if (ix.hashes && ix.n > 0)
-      HIP_CHECK(hipMemcpyAsync(nb->p, ix.hashes->p, 8 * ix.n, hipMemcpyDeviceToDevice, s->stream));
-    ix.hashes = nb;
-    ix.hash_cap = cap;
-  }
+  s->dict.reserve(ix.hashes, ix.hash_cap, n, 4096, 8, ix.n);  // the hashes so far move with it
   const int64_t m = (int64_t)(n - ix.n);
   if (m > 0) {
     double by = 16.0 * (double)m;  // the strings' bytes, one offset and one hash per string
-    if (s->profiling) {
-      std::lock_guard<std::mutex> lk(s->str_mu);
-      for (size_t c = ix.n; c < n; ++c) by += (double)s->strings[c].size();
-    }
+    if (s->profiling) by += s->dict.bytes_of(nullptr, (int64_t)ix.n, m, (int64_t)n);
     KernelTimer kt(s, "str_idx_hash", by);
     hipLaunchKernelGGL(k_str_hash, dim3(grid_for(m, SF_BLOCK)), dim3(SF_BLOCK), 0, s->stream, off, bytes,
                        (int64_t)ix.n, (int64_t)n, (uint64_t *)ix.hashes->p);
@@ -585,7 +575,7 @@ static BufPtr intern_results(Session *s, const StringHeap &h, size_t n0, const i
   const uint8_t *bytes = (const uint8_t *)h.bytes->p;
   const dim3 grid(grid_for(n, SF_BLOCK)), block(SF_BLOCK);
   ensure_index(s, h, n0);
-  const Session::StrIndex &ix = s->str_index;
+  const StringDict::Index &ix = s->dict.index;
   BufPtr rhash = s->alloc(8 * (size_t)n), d_out = s->alloc(8 * (size_t)n), grp = s->alloc(8 * (size_t)n);
   {
     KernelTimer kt(s, "str_fn_hash", (double)total + 16.0 * (double)n);
@@ -642,8 +632,8 @@ static BufPtr intern_results(Session *s, const StringHeap &h, size_t n0, const i
     HIP_CHECK(hipMemcpyAsync(host.data(), stage->p, stage_size, hipMemcpyDeviceToHost, s->stream));
     if (out) HIP_CHECK(hipMemcpyAsync(out, d_out->p, 8 * (size_t)n, hipMemcpyDeviceToHost, s->stream));
     s->sync();
-    string_heap_append(s, n0, h.nbytes, (const int64_t *)stage->p, (const uint8_t *)stage->p + sbytes_at,
-                       (const int64_t *)host.data(), host.data() + sbytes_at, n_new, nb, codes);
+    s->dict.heap_append(h, (const int64_t *)stage->p, (const uint8_t *)stage->p + sbytes_at,
+                        (const int64_t *)host.data(), host.data() + sbytes_at, n_new, nb, codes);
     // codes other than n0 + rank: another thread interned meanwhile (the host map resolved them)
     bool moved = false;
     for (int64_t r = 0; r < n_new; ++r) moved |= codes[(size_t)r] != (int64_t)n0 + r;
@@ -676,9 +666,9 @@ void string_fn_codes(Session *s, int32_t fn, int64_t iarg0, int64_t iarg1, int64
                      const int64_t *src, int64_t c0, int64_t n, int64_t *out) {
   if (fn < CAPF_STR_FN_UPPER || fn > CAPF_STR_FN_REPLACE) illegal("unknown string function");
   if (fn == CAPF_STR_FN_SUBSTRING && iarg1 < 0) illegal("negative substring length");
-  std::lock_guard<std::mutex> index_lock(s->index_mu);
-  size_t n0 = 0;
-  const StringHeap h = string_heap(s, &n0);  // the snapshot the whole step works against
+  std::lock_guard<std::mutex> index_lock(s->dict.index_mu);
+  const StringHeap h = s->dict.heap();  // the snapshot the whole step works against
+  const size_t n0 = h.n;
   const bool concat = fn == CAPF_STR_FN_CONCAT_L || fn == CAPF_STR_FN_CONCAT_R;
   if ((concat || fn == CAPF_STR_FN_REPLACE) && (lit0 < 0 || (size_t)lit0 >= n0)) illegal("unknown string code");
   if (fn == CAPF_STR_FN_REPLACE && (lit1 < 0 || (size_t)lit1 >= n0)) illegal("unknown string code");
@@ -688,16 +678,8 @@ void string_fn_codes(Session *s, int32_t fn, int64_t iarg0, int64_t iarg1, int64
   } else if (n > 0 && (c0 < 0 || c0 > (int64_t)n0 || n > (int64_t)n0 - c0)) {
     illegal("unknown string code");
   }
-  double src_bytes = 0;
-  {
-    std::lock_guard<std::mutex> lk(s->str_mu);
-    if (fn == CAPF_STR_FN_REPLACE && s->strings[(size_t)lit0].empty()) illegal("empty search literal");
-    if (s->profiling)
-      for (int64_t i = 0; i < n; ++i) {
-        const int64_t c = src ? src[i] : c0 + i;
-        if (c >= 0) src_bytes += (double)s->strings[(size_t)c].size();
-      }
-  }
+  if (fn == CAPF_STR_FN_REPLACE && s->dict.empty(lit0)) illegal("empty search literal");
+  const double src_bytes = s->profiling ? s->dict.bytes_of(src, c0, n, (int64_t)n0) : 0;
   if (n == 0) return;
   // substring's arguments brought within ±2^41 (no string has that many units)
   // without changing the range they select, so the kernels' sums cannot overflow
@@ -950,14 +932,10 @@ static double split_source_bytes(Session *s, const SplitArgs &g, int64_t n) {
   };
   std::vector<uint8_t> b0, b1, b2, b3;
   const ColView hs = host_view(g.s, b0, b1), hd = host_view(g.d, b2, b3);
-  double by = 0;
-  std::lock_guard<std::mutex> lk(s->str_mu);
-  for (int64_t r = 0; r < n; ++r) {
-    if ((hs.valid && !hs.valid[r]) || (hd.valid && !hd.valid[r])) continue;
-    const int64_t c = ld_int(hs, r);
-    if (c >= 0 && c < g.n0) by += (double)s->strings[(size_t)c].size();
-  }
-  return by;
+  std::vector<int64_t> codes;
+  for (int64_t r = 0; r < n; ++r)
+    if (!(hs.valid && !hs.valid[r]) && !(hd.valid && !hd.valid[r])) codes.push_back(ld_int(hs, r));
+  return s->dict.bytes_of(codes.data(), 0, (int64_t)codes.size(), g.n0);
 }
 
 ColPtr str_split_column(Session *s, const Data &d, int subject_col, int delim_col) {
@@ -971,9 +949,9 @@ ColPtr str_split_column(Session *s, const Data &d, int subject_col, int delim_co
   o->child = make_column(s, Type::String, 0, false);
   if (n == 0) return o;
   SplitArgs g{view_of(sc), view_of(dc), 0};
-  std::lock_guard<std::mutex> index_lock(s->index_mu);
-  size_t n0 = 0;
-  const StringHeap h = string_heap(s, &n0);  // the snapshot the whole step works against
+  std::lock_guard<std::mutex> index_lock(s->dict.index_mu);
+  const StringHeap h = s->dict.heap();  // the snapshot the whole step works against
+  const size_t n0 = h.n;
   g.n0 = (int64_t)n0;
   const double src_bytes = s->profiling ? split_source_bytes(s, g, n) : 0;
   const int64_t long_len = string_long_threshold();

@@ -2,8 +2,8 @@
 // answered once per dictionary string (CAPF_OP_STR_MATCH's dictionary path).
 //
 // All rows holding the same subject code share one answer, so a literal
-// pattern is matched against the session's device string heap (runtime.cpp
-// string_heap) — one uint8 per dictionary code, 0 false / 1 true — and the
+// pattern is matched against the session's device string heap (string_dict.h
+// heap()) — one uint8 per dictionary code, 0 false / 1 true — and the
 // prepared program looks the answer up by subject code.  The table is cached
 // per (kind, pattern code) and, the dictionary being append-only, extended
 // over the codes interned since (at most STR_MATCH_TABLES tables are kept,
@@ -102,10 +102,7 @@ static void fill_match_table(Session *s, const StringHeap &h, int kind, int64_t 
   }
   // profiled bytes: the strings' bytes, one offset and one answer per string
   double heap_bytes = 9.0 * (double)m;
-  if (s->profiling) {
-    std::lock_guard<std::mutex> lk(s->str_mu);
-    for (int64_t c = c0; c < c1; ++c) heap_bytes += (double)s->strings[(size_t)c].size();
-  }
+  if (s->profiling) heap_bytes += s->dict.bytes_of(nullptr, c0, m, c1);
   {
     KernelTimer kt(s, "str_match", heap_bytes);
     hipLaunchKernelGGL(k_str_match, dim3(grid_for(m, SM_BLOCK)), dim3(SM_BLOCK), 0, s->stream, off, bytes, c0, c1,
@@ -125,8 +122,9 @@ static void fill_match_table(Session *s, const StringHeap &h, int kind, int64_t 
   KERNEL_CHECK();
 }
 
-static Session::StrMatchTable *find_table(Session *s, int kind, int64_t pcode) {
-  for (auto &t : s->match_tables)
+// (match_mu held)
+static StringDict::MatchTable *find_table(Session *s, int kind, int64_t pcode) {
+  for (auto &t : s->dict.match_tables)
     if (t.kind == kind && t.pattern == pcode) return &t;
   return nullptr;
 }
@@ -135,38 +133,29 @@ bool string_match_by_table(Session *s, int kind, int64_t pattern_code, int64_t n
   const char *mode = getenv("CAPF_STR_MATCH");
   if (mode && strcmp(mode, "rows") == 0) return false;
   if (mode && strcmp(mode, "dict") == 0) return true;
-  size_t n = 0, covered = 0;
+  const size_t n = s->dict.size();
+  size_t covered = 0;
   {
-    std::lock_guard<std::mutex> lk(s->str_mu);
-    n = s->strings.size();
-  }
-  {
-    std::lock_guard<std::mutex> lk(s->match_mu);
+    std::lock_guard<std::mutex> lk(s->dict.match_mu);
     if (const auto *t = find_table(s, kind, pattern_code)) covered = t->n;
   }
   return (int64_t)(n - std::min(n, covered)) <= nrows;
 }
 
 BufPtr string_match_table(Session *s, int kind, int64_t pattern_code, size_t *n_out) {
-  size_t n = 0;
-  const StringHeap h = string_heap(s, &n);
+  const StringHeap h = s->dict.heap();
+  const size_t n = h.n;
   if (kind < 0 || kind > 2) illegal("string predicate kind out of range");
   if (pattern_code < 0 || (size_t)pattern_code >= n) illegal("unknown string code");
-  std::lock_guard<std::mutex> lk(s->match_mu);
+  std::lock_guard<std::mutex> lk(s->dict.match_mu);
+  auto &tables = s->dict.match_tables;
   if (!find_table(s, kind, pattern_code)) {
-    if (s->match_tables.size() >= STR_MATCH_TABLES) s->match_tables.erase(s->match_tables.begin());
-    s->match_tables.push_back(Session::StrMatchTable{kind, pattern_code, nullptr, 0, 0});
+    if (tables.size() >= STR_MATCH_TABLES) tables.erase(tables.begin());
+    tables.push_back(StringDict::MatchTable{kind, pattern_code, nullptr, 0, 0});
   }
-  Session::StrMatchTable &t = *find_table(s, kind, pattern_code);
+  StringDict::MatchTable &t = *find_table(s, kind, pattern_code);
   if (n > t.n) {
-    if (n > t.cap) {  // geometric; the answers so far move device to device
-      const size_t cap = std::max<size_t>(2 * t.cap, std::max<size_t>(n, 4096));
-      BufPtr nb = s->alloc(cap);
-      if (t.buf && t.n > 0)
-        HIP_CHECK(hipMemcpyAsync(nb->p, t.buf->p, t.n, hipMemcpyDeviceToDevice, s->stream));
-      t.buf = nb;
-      t.cap = cap;
-    }
+    s->dict.reserve(t.buf, t.cap, n, 4096, 1, t.n);  // the answers so far move with it
     fill_match_table(s, h, kind, pattern_code, (int64_t)t.n, (int64_t)n, (uint8_t *)t.buf->p);
     t.n = n;
   }
