@@ -144,6 +144,7 @@ _SIGS = {
     "capf_var_length_reach_undirected": (c_int32, [_S, _T, c_char_p, c_char_p, _T, c_char_p, _T, c_char_p,
                                                    c_int32, c_int32, c_char_p, c_char_p, _PT]),
     "capf_chain2_hist_len": (c_int64, [c_int64]),
+    "capf_c5_job_len": (c_uint32, [c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32]),
     "capf_chain2_local_hists": (c_int32, [_S, _T, c_char_p, c_char_p, c_int64, c_int64, c_void_p,
                                           c_void_p, POINTER(c_int64)]),
     "capf_table_node_partition_diag": (c_int32, [_T, c_char_p, c_char_p, c_int64, c_int64, c_int32, c_int32, _PT,

@@ -62,6 +62,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "c5_job_len.h"
 #include "capf_internal.h"
 #include "device_common.h"
 
@@ -678,6 +679,10 @@ struct C5Steal {
   uint32_t *cursor;       // [nslots] next tile of the slot's out-run
   uint32_t *jobt;         // [nslots] IDX: tiles per job of the slot, 0 until its unit has set it
   uint4 *images;          // [nslots] × C5_IMAGE_BYTES
+  // IDX, the two-zone rule (c5_job_len.h): a run above the mean by a crumb's weight or more
+  uint32_t job_split = 0;     // J: jobs of a mean run (job_pieces = mean / J)
+  uint32_t excess_split = 0;  // X: crumbs to the weight of a base job (0: one zone)
+  uint32_t *jobx = nullptr;   // [nslots] tiles per job from tile J · jobt[slot] on; 0: jobt[slot] throughout
 };
 
 struct C5Probe {
@@ -1140,7 +1145,9 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
       // header): one pass over the run's 4·ntiles B of meta, as the heavy
       // publishers of mode P make.  The run is cut into k = round(T / job_pieces)
       // ranges of ⌈ntiles / k⌉ tiles (work per tile is taken as uniform within a
-      // run), not shorter than job_tiles.  T = 0: one job that walks nothing.
+      // run), not shorter than job_tiles; a run above the mean by a crumb's weight
+      // gets a second, shorter length for the tiles that hold its excess
+      // (c5_job_lens).  T = 0: one job that walks nothing.
       // Everything stays in the mailbox: no register lives across the walks.
       if (st->job_pieces) {
         const uint32_t bk = ((const uint32_t *)(st->images + (int64_t)ui * (C5_IMAGE_BYTES / 16) + 2 * C2_BW / 16))[1];
@@ -1151,10 +1158,10 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
         if (lane == 0 && q) atomicAdd(&job[CJ_POUT], (int)q);
         __syncthreads();
         if (threadIdx.x == 0) {
-          const uint32_t T = (uint32_t)job[CJ_POUT], W = st->job_pieces, nt = (uint32_t)ntiles;
-          const uint32_t k = max(1u, (uint32_t)(((unsigned long long)T + W / 2) / W));
-          const uint32_t jt = min(nt, max(st->job_tiles, (nt + k - 1) / k));
-          __hip_atomic_store(&st->jobt[ui], jt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const C5JobLens jl = c5_job_lens((uint32_t)job[CJ_POUT], st->job_pieces, st->job_split, st->excess_split,
+                                           (uint32_t)ntiles, st->job_tiles);
+          if (jl.crumb) __hip_atomic_store(&st->jobx[ui], jl.crumb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(&st->jobt[ui], jl.base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
     } else {
@@ -1359,11 +1366,12 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
     // for another, and every cursor add that fails retires its slot for good,
     // so the search ends).
     // A slot's cursor counts tiles.  A taker picks a length jl (mode P: job_tiles;
-    // IDX: jobt[slot], or job_tiles while that is still 0) and adds it: the add
+    // IDX: jobt[slot] or, past the slot's base zone, jobx[slot] — c5_job_pick — or
+    // job_tiles while jobt[slot] is still 0) and adds it: the add
     // returns a start c no other add returns and moves the cursor by exactly
     // the jl it claims, so the ranges [c, min(c + jl, ntiles)) of the adds with
     // c < ntiles are disjoint and cover [0, ntiles) whatever jl each taker used;
-    // an add with c ≥ ntiles has failed.  jobt[] therefore needs no ordering
+    // an add with c ≥ ntiles has failed.  jobt[] and jobx[] therefore need no ordering
     // (relaxed store, relaxed loads): any value read gives a correct partition,
     // the word only steers the jobs' sizes.  (A slot sees at most one failed
     // add per unit, each ≤ ntiles: the cursor stays below 2^32.)
@@ -1379,12 +1387,14 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
       if (wave == 0) {
         const uint32_t nt = (uint32_t)ntiles;
         // lane 0 draws a job from slot sl's cursor: its first tile (≥ nt: none left) and its length
-        auto draw = [&](uint32_t sl, uint32_t *len) -> uint32_t {
+        // (pos: where the cursor was last seen — it picks the zone's length, stale or not)
+        auto draw = [&](uint32_t sl, uint32_t pos, uint32_t *len) -> uint32_t {
           uint32_t jl = sb->job_tiles, c = 0;
           if (lane == 0) {
             if constexpr (IDX) {
               const uint32_t w = __hip_atomic_load(&sb->jobt[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              jl = w ? w : jl;
+              const uint32_t x = __hip_atomic_load(&sb->jobx[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              jl = c5_job_pick(w, x, sb->job_split, jl, pos);
             }
             c = atomicAdd(&sb->cursor[sl], jl);
           }
@@ -1398,7 +1408,8 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
           found = CJ_OWN;
         } else if (sb->steal) {
           if (cur >= 0) {
-            const uint32_t c = draw((uint32_t)cur, &jlen);
+            // (the cursor is at or past the end of the job this unit drew from it last)
+            const uint32_t c = draw((uint32_t)cur, (uint32_t)(jb[CJ_T0] + jb[CJ_LEN]), &jlen);
             if (c < nt) found = cur, jt0 = c;
           }
           if (found < 0) {
@@ -1410,12 +1421,15 @@ __global__ __launch_bounds__(C5_BLOCK) void k_c5_gather(const C3Unit *units,
               bool cand = sl < nsl;
               if (!IDX && cand)
                 cand = __hip_atomic_load(&sb->ready[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-              if (cand) cand = __hip_atomic_load(&sb->cursor[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nt;
+              uint32_t cv = nt;
+              if (cand) cv = __hip_atomic_load(&sb->cursor[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              cand = cv < nt;
               unsigned long long mask = __builtin_amdgcn_ballot_w64(cand);
               while (mask && found < 0) {
-                const uint32_t sc = s0 + (uint32_t)__builtin_ctzll(mask);
+                const int ln = __builtin_amdgcn_readfirstlane(__builtin_ctzll(mask));
+                const uint32_t sc = s0 + (uint32_t)ln;
                 mask &= mask - 1;
-                const uint32_t c = draw(sc, &jlen);
+                const uint32_t c = draw(sc, (uint32_t)__builtin_amdgcn_readlane((int)cv, ln), &jlen);
                 if (c < nt) found = (int)sc, jt0 = c;
               }
             }
@@ -1585,7 +1599,7 @@ static void launch_c5(Session *s, const C5Cols<W> &c, uint16_t *part, uint32_t *
 // Work area of the post-P1 kernels: run_total[nr] (uint64) | counters (8 ×
 // int32: [0] units, [1] hand-off events, [2] image slots claimed, [3] steals,
 // [4] jobs) | hand-off log | split[nr] | ready[slots], cursor[slots],
-// jobt[slots] | units | images.
+// jobt[slots], jobx[slots] | units | images.
 // Byte offsets; the first `zero_bytes` must start at zero — the run totals and
 // counters are added to, a reserved log slot may be read before its owner
 // wrote it (a zero entry adds nothing), and the split flags are read by the
@@ -1616,7 +1630,7 @@ static C5PostLayout c5_post_layout(int nr, int S, int split_x16, int64_t nkeys, 
   l.split = l.log + 8 * (int64_t)l.ovf_cap;
   l.steal_slots = steal_slots;
   l.steal_ctl = l.split + 4 * (int64_t)nr;  // nr = 2·nb is even: 8-B aligned like the log
-  l.units = (l.steal_ctl + 12 * (int64_t)steal_slots + 7) & ~int64_t(7);
+  l.units = (l.steal_ctl + 16 * (int64_t)steal_slots + 7) & ~int64_t(7);
   l.images = (l.units + (int64_t)sizeof(C3Unit) * l.max_units + 15) & ~int64_t(15);
   l.bytes = l.images + (images_external ? 0 : (int64_t)C5_IMAGE_BYTES * steal_slots);
   l.zero_bytes = l.units;
@@ -1670,14 +1684,17 @@ struct C5StealKnobs {
   double theta;        // CAPF_C5_STEAL_THETA: heavy = more than (1 + theta) × the mean pieces in a run
   uint32_t tiles;      // CAPF_C5_STEAL_TILES: tiles per job (mode P); the shortest job (indexed units); 0 = unset
   uint32_t job_split;  // CAPF_C5_JOB_SPLIT: indexed units cut a mean out-run into this many jobs (0: jobs of `tiles`)
+  uint32_t excess_split;  // CAPF_C5_EXCESS_SPLIT: crumbs to the weight of one such job, for the part of a heavy
+                          // out-run above the mean (0: one length per run)
 };
 constexpr uint32_t C5_JOB_TILES = 512;     // mode P
 constexpr uint32_t C5_IDX_MIN_TILES = 32;  // indexed units (profiles/index_jobs_sweep.txt)
 constexpr uint32_t C5_IDX_JOB_SPLIT = 4;
+constexpr uint32_t C5_IDX_EXCESS_SPLIT = 2;  // (profiles/index_excess_sweep.txt)
 
 static C5StealKnobs c5_steal_knobs() {
   const char *se = getenv("CAPF_C5_STEAL"), *te = getenv("CAPF_C5_STEAL_TILES"), *th = getenv("CAPF_C5_STEAL_THETA");
-  const char *js = getenv("CAPF_C5_JOB_SPLIT");
+  const char *js = getenv("CAPF_C5_JOB_SPLIT"), *xs = getenv("CAPF_C5_EXCESS_SPLIT");
   C5StealKnobs k;
   k.steal = !se                    ? C5_STEAL_HEAVY
             : !strcmp(se, "all")    ? C5_STEAL_ALL
@@ -1687,6 +1704,7 @@ static C5StealKnobs c5_steal_knobs() {
   k.theta = th ? atof(th) : 0.15;
   k.tiles = te ? (uint32_t)std::max(1, atoi(te)) : 0u;
   k.job_split = js ? (uint32_t)std::max(0, atoi(js)) : C5_IDX_JOB_SPLIT;
+  k.excess_split = xs ? (uint32_t)std::min(64, std::max(0, atoi(xs))) : C5_IDX_EXCESS_SPLIT;
   return k;
 }
 
@@ -2086,7 +2104,9 @@ static void chain2_c5_indexed(Session *s, C5Cols<W> c, const C5InIndex &ix, unsi
   uint32_t *sctl = (uint32_t *)(base + l.steal_ctl);
   const C3Ovf ovf{(uint2 *)(base + l.log), (uint32_t *)(counters + 1), l.ovf_cap};
   // Jobs of equal work: a mean out-run is cut into job_split jobs, a run of x times
-  // the mean into ~x · job_split, none shorter than min_tiles (C5Steal::job_pieces).
+  // the mean into ~x · job_split, none shorter than min_tiles (C5Steal::job_pieces);
+  // a run above the mean by 1 / (job_split · excess_split) of it or more into job_split
+  // jobs for its first mean's worth of tiles and excess_split times finer ones for the rest.
   const C5StealKnobs k = c5_steal_knobs();
   const uint32_t min_tiles = k.tiles ? k.tiles : C5_IDX_MIN_TILES;
   const uint32_t job_pieces =
@@ -2094,7 +2114,7 @@ static void chain2_c5_indexed(Session *s, C5Cols<W> c, const C5InIndex &ix, unsi
   const C5Probe pr{d_acc3, spill->fin, nullptr, C5_HOT,
                    C5Steal{C5_STEAL_ALL, min_tiles, (uint32_t)c.nb, 0, job_pieces, (uint32_t *)(counters + 2),
                            (uint32_t *)(counters + 3), (uint32_t *)(counters + 4), sctl, sctl + c.nb, sctl + 2 * c.nb,
-                           ix.images()},
+                           ix.images(), k.job_split, k.excess_split, sctl + 3 * c.nb},
                    ix.loops()};
   const C3Sides sd{c.nb, {0, 0}, {c.ntiles, c.ntiles}, 32, 0, 0, nullptr};
   {
@@ -2925,3 +2945,9 @@ bool bits_count_partitioned(Session *s, const ColView &key, int64_t n, int64_t l
 }
 
 }  // namespace capf
+
+// The indexed units' job-length rule (c5_job_len.h) for a host-side check: no device is touched.
+extern "C" uint32_t capf_c5_job_len(uint32_t run_pieces, uint32_t mean_pieces, uint32_t job_split,
+                                    uint32_t excess_split, uint32_t ntiles, uint32_t min_tiles, uint32_t pos) {
+  return capf::c5_job_len(run_pieces, mean_pieces, job_split, excess_split, ntiles, min_tiles, pos);
+}

@@ -615,6 +615,15 @@ capf_status capf_chain2_local_hists(capf_session *s, capf_table *rels, const cha
                                     const char *dst_col, int64_t node_base, int64_t n_nodes,
                                     uint32_t *d_in_hist, uint32_t *d_out_hist,
                                     int64_t *self_loops);
+/* Diagnostics, host only (no device is touched): the length in tiles of the
+ * job that a unit of the indexed 2-hop count claims from an out-run of `ntiles`
+ * tiles holding `run_pieces` pieces, when it last saw the run's cursor at tile
+ * `pos`.  mean_pieces: a mean run's pieces; job_split: the jobs a mean run is cut
+ * into (CAPF_C5_JOB_SPLIT); excess_split: crumbs to the weight of one such job
+ * for the part of a run above the mean (CAPF_C5_EXCESS_SPLIT, 0: one length per
+ * run); min_tiles: the shortest job (CAPF_C5_STEAL_TILES).                  */
+uint32_t capf_c5_job_len(uint32_t run_pieces, uint32_t mean_pieces, uint32_t job_split,
+                         uint32_t excess_split, uint32_t ntiles, uint32_t min_tiles, uint32_t pos);
 /* Σ_v a[v]·b[v] over n entries (device uint32 arrays), exact in uint64. */
 capf_status capf_dot_u32(capf_session *s, const uint32_t *d_a, const uint32_t *d_b, int64_t n,
                          uint64_t *out);

@@ -739,6 +739,11 @@ JNI(void, triangleCountPart)(JNIEnv *env, jobject, jlong s, jlong rels, jstring 
                                      reinterpret_cast<int64_t *>(d_count)));
 }
 JNI(jlong, chain2HistLen)(JNIEnv *, jobject, jlong n_nodes) { return capf_chain2_hist_len(n_nodes); }
+JNI(jlong, c5JobLen)(JNIEnv *, jobject, jlong run_pieces, jlong mean_pieces, jlong job_split, jlong excess_split,
+                     jlong ntiles, jlong min_tiles, jlong pos) {
+  return (jlong)capf_c5_job_len((uint32_t)run_pieces, (uint32_t)mean_pieces, (uint32_t)job_split,
+                                (uint32_t)excess_split, (uint32_t)ntiles, (uint32_t)min_tiles, (uint32_t)pos);
+}
 JNI(jlong, chain2LocalHists)(JNIEnv *env, jobject, jlong s, jlong rels, jstring src_col,
                              jstring dst_col, jlong node_base, jlong n_nodes, jlong d_in,
                              jlong d_out) {

@@ -230,6 +230,9 @@ object Native {
   @native def triangleCountPart(session: Long, rels: Long, srcCol: String, dstCol: String, nodeBase: Long,
                                 nNodes: Long, parts: Int, part: Int, dCount: Long): Unit
   @native def chain2HistLen(nNodes: Long): Long
+  /** Diagnostics, host only: the tiles of the job an indexed 2-hop unit claims (capf_c5_job_len; uint32 values). */
+  @native def c5JobLen(runPieces: Long, meanPieces: Long, jobSplit: Long, excessSplit: Long, nTiles: Long,
+                       minTiles: Long, pos: Long): Long
   @native def chain2LocalHists(session: Long, rels: Long, srcCol: String, dstCol: String, nodeBase: Long,
                                nNodes: Long, dIn: Long, dOut: Long): Long
   @native def dotU32(session: Long, dA: Long, dB: Long, n: Long): Long

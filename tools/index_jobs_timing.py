@@ -10,8 +10,8 @@ Two graphs, FOR24 ids, 16 << S rels (S = 24: the headline shape):
           tests/test_two_hop_jobs.py) — one out-run ≈150 × the mean.  Drawn on
           the host and uploaded once per process.
 
-A variant is a knob setting, NAME:VAR=VALUE,VAR=VALUE (the knobs are read per
-query); `default` sets nothing.  Every library (--libs: file names beside the
+A variant is a knob setting, NAME:VAR=VALUE,VAR=VALUE (the knobs, CAPF_C5_JOB_SPLIT,
+CAPF_C5_STEAL_TILES and CAPF_C5_EXCESS_SPLIT, are read per query); `default` sets nothing.  Every library (--libs: file names beside the
 package's own, loaded through CAPF_LIB_AB; default: this build) gets ONE
 process, which builds both graphs, runs the first (index-building) query, and
 then takes the variants in turn, round after round (--rounds ≥ 2): per variant
@@ -30,8 +30,9 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT_VARIANTS = "default;" + ";".join(
-    f"split{j}_tiles{t}:CAPF_C5_JOB_SPLIT={j},CAPF_C5_STEAL_TILES={t}" for j in (2, 4, 8) for t in (16, 32, 64))
-KNOBS = ("CAPF_C5_JOB_SPLIT", "CAPF_C5_STEAL_TILES")
+    [f"split{j}_tiles{t}:CAPF_C5_JOB_SPLIT={j},CAPF_C5_STEAL_TILES={t}" for j in (2, 4, 8) for t in (16, 32, 64)] +
+    [f"excess{x}_tiles{t}:CAPF_C5_EXCESS_SPLIT={x},CAPF_C5_STEAL_TILES={t}" for x in (0, 1, 2, 4, 8) for t in (16, 32, 64)])
+KNOBS = ("CAPF_C5_JOB_SPLIT", "CAPF_C5_STEAL_TILES", "CAPF_C5_EXCESS_SPLIT")
 
 
 def parse_variants(spec):
