@@ -39,6 +39,11 @@ class IllegalStateException(CypherException):
     pass
 
 
+class UnsupportedOperationException(CypherException):
+    """okapi's UnsupportedOperationException: an unknown temporal or duration
+    accessor (TemporalConversions.scala:172, TemporalUdfs.scala:145)."""
+
+
 class HipRuntimeException(CypherException):
     pass
 

@@ -55,8 +55,14 @@ enum class Type : int32_t {
   Float64 = CAPF_TYPE_FLOAT64,
   Bool = CAPF_TYPE_BOOL,
   String = CAPF_TYPE_STRING,
-  List = CAPF_TYPE_LIST  // data = int64 offsets [n + 1], child = the elements
+  List = CAPF_TYPE_LIST,  // data = int64 offsets [n + 1], child = the elements
+  Date = CAPF_TYPE_DATE,                    // int64 days since 1970-01-01
+  LocalDateTime = CAPF_TYPE_LOCALDATETIME   // int64 microseconds since 1970-01-01T00:00:00
 };
+inline bool is_temporal(Type t) { return t == Type::Date || t == Type::LocalDateTime; }
+// columns whose values are plain int64 to every kernel that moves, orders or
+// hashes them (ld_int, the FOR encodings, min / max statistics)
+inline bool is_int_payload(Type t) { return t == Type::Int64 || is_temporal(t); }
 inline size_t type_width(Type t) { return t == Type::Bool ? 1 : (t == Type::Null ? 0 : 8); }
 const char *type_name(Type t);
 
@@ -181,7 +187,9 @@ enum Op : int32_t {
   OP_TO_BOOLEAN = CAPF_OP_TO_BOOLEAN, OP_IN_SET = CAPF_OP_IN_SET, OP_STR_MAP = CAPF_OP_STR_MAP,
   OP_VALUE_MAP = CAPF_OP_VALUE_MAP, OP_STR_TO_NUM = CAPF_OP_STR_TO_NUM, OP_RAND = CAPF_OP_RAND,
   OP_LIST_INDEX = CAPF_OP_LIST_INDEX, OP_STR_RANK = CAPF_OP_STR_RANK,
-  OP_STR_MATCH = CAPF_OP_STR_MATCH, OP_IN_LIST = CAPF_OP_IN_LIST, OP_LAMBDA = CAPF_OP_LAMBDA
+  OP_STR_MATCH = CAPF_OP_STR_MATCH, OP_IN_LIST = CAPF_OP_IN_LIST, OP_LAMBDA = CAPF_OP_LAMBDA,
+  OP_LIT_TEMPORAL = CAPF_OP_LIT_TEMPORAL, OP_TEMPORAL_FIELD = CAPF_OP_TEMPORAL_FIELD,
+  OP_TEMPORAL_ADD = CAPF_OP_TEMPORAL_ADD
 };
 // a program name that refers to a session literal set ("\x01set:<id>"), not a column
 inline bool is_literal_set_name(const std::string &nm) { return nm.size() > 5 && nm.compare(0, 5, "\x01set:") == 0; }

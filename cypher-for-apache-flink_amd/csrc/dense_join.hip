@@ -130,7 +130,7 @@ static std::shared_ptr<DenseIndex> hashed_index(Session *s, const ColPtr &c, int
 // but sparse; nullptr when neither applies.
 static std::shared_ptr<DenseIndex> dense_index(Session *s, const ColPtr &c, int64_t nrows) {
   force(c);
-  if (c->type != Type::Int64 || c->lazy || nrows == 0 || nrows >= (int64_t(1) << 31)) return nullptr;
+  if (!is_int_payload(c->type) || c->lazy || nrows == 0 || nrows >= (int64_t(1) << 31)) return nullptr;
   {
     std::lock_guard<std::mutex> lk(c->mu);
     if (c->dense) {
@@ -259,7 +259,7 @@ bool dense_join_possible(Session *s, const Data &l, const Data &r, const std::ve
   if (!di && r_ok && r.nrows > l.nrows) di = dense_index(s, r.cols[keys[0].second], r.nrows);
   if (!di) return false;
   const ColPtr &pk = (build_left ? r : l).cols[build_left ? keys[0].second : keys[0].first];
-  return pk->type == Type::Int64;  // (a lazy column carries its type: no gather here)
+  return is_int_payload(pk->type);  // (a lazy column carries its type: no gather here)
 }
 
 bool dense_join(Session *s, const Data &l, const Data &r, const std::vector<std::pair<int, int>> &keys,
@@ -283,7 +283,7 @@ bool dense_join(Session *s, const Data &l, const Data &r, const std::vector<std:
   const ColPtr &pk = Pr.cols[build_left ? keys[0].second : keys[0].first];
   // not forced: a lazy probe key (a join's output column) may be provably
   // matching from its source's statistics, and then it is never gathered
-  if (pk->type != Type::Int64) return false;
+  if (!is_int_payload(pk->type)) return false;
   const int64_t n = Pr.nrows;
   const bool probe_outer = join_type != CAPF_JOIN_INNER;
   // every probe key provably matches (no NULL, the key's range inside the dense

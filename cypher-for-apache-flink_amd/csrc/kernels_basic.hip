@@ -710,7 +710,7 @@ ColPtr decode_column(Session *s, const ColPtr &c) {
 // 24 bits, else FOR32 where it fits 32.  Already-encoded columns unchanged.
 ColPtr encode_column(Session *s, const ColPtr &c, int width) {
   force(c);
-  if (c->enc != ENC_PLAIN || (c->type != Type::Int64 && c->type != Type::String) || c->n == 0)
+  if (c->enc != ENC_PLAIN || (!is_int_payload(c->type) && c->type != Type::String) || c->n == 0)
     return c;
   const ColStats &st = column_stats(s, c);
   if (st.non_null == 0 || (uint64_t)(st.max - st.min) > 0xFFFFFFFFull) return c;
@@ -823,7 +823,7 @@ __global__ __launch_bounds__(256) void k_dup_check(ColView v, int64_t n, int64_t
 
 ColStats compute_stats(Session *s, const Column &c) {
   ColStats st;
-  if (c.type != Type::Int64 && c.type != Type::String) {
+  if (!is_int_payload(c.type) && c.type != Type::String) {
     st.non_null = c.type == Type::Null ? 0 : c.n;
     return st;
   }
@@ -946,6 +946,126 @@ __device__ inline Val math1(int32_t op, const Val &a) {
     case OP_RADIANS: return mkf(x / 180.0 * 3.141592653589793);
     default: return mknull(CAPF_TYPE_FLOAT64);
   }
+}
+
+// ------------------------------------------------------ temporal values
+// DATE = days, LOCALDATETIME = microseconds since 1970-01-01[T00:00:00] in the
+// proleptic ISO calendar (java.time's; DESIGN.md "Temporal values").  One
+// int64 floor division splits the day number off a LOCALDATETIME; from there
+// the calendar is 32-bit arithmetic with divisions by constants only: no loop
+// over years or months and no table.  Values outside years 0001-9999 give
+// unspecified results (never an access: nothing here reads memory).
+constexpr int64_t MICROS_PER_DAY = 86400000000ll;
+
+struct Civil {
+  int32_t y, m, d;
+};
+
+__device__ inline int32_t floor_div(int32_t a, int32_t b) { return (a >= 0 ? a : a - (b - 1)) / b; }
+__device__ inline int64_t floor_div64(int64_t a, int64_t b) { return (a >= 0 ? a : a - (b - 1)) / b; }
+__device__ inline bool leap_year(int32_t y) { return (y & 3) == 0 && (y % 100 != 0 || y % 400 == 0); }
+
+// Day number → civil date by the era / day-of-era method: eras of 400 years
+// (146 097 days) from 0000-03-01, the year beginning in March so the leap day
+// is its last.
+__device__ inline Civil civil_from_days(int32_t z) {
+  z += 719468;  // days from 0000-03-01 to 1970-01-01
+  const int32_t era = floor_div(z, 146097);
+  const uint32_t doe = (uint32_t)(z - era * 146097);                           // [0, 146096]
+  const uint32_t yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;  // [0, 399]
+  const uint32_t doy = doe - (365 * yoe + yoe / 4 - yoe / 100);                // [0, 365], from March 1
+  const uint32_t mp = (5 * doy + 2) / 153;                                     // [0, 11], March = 0
+  Civil c;
+  c.d = (int32_t)(doy - (153 * mp + 2) / 5 + 1);
+  c.m = (int32_t)(mp < 10 ? mp + 3 : mp - 9);
+  c.y = (int32_t)yoe + era * 400 + (c.m <= 2 ? 1 : 0);
+  return c;
+}
+
+__device__ inline int32_t days_from_civil(int32_t y, int32_t m, int32_t d) {
+  y -= m <= 2 ? 1 : 0;
+  const int32_t era = floor_div(y, 400);
+  const uint32_t yoe = (uint32_t)(y - era * 400);
+  const uint32_t doy = (153u * (uint32_t)(m > 2 ? m - 3 : m + 9) + 2) / 5 + (uint32_t)d - 1;
+  const uint32_t doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
+  return era * 146097 + (int32_t)doe - 719468;
+}
+
+// 1-based day of the year of (m, d)
+__device__ inline int32_t ordinal_day(bool leap, int32_t m, int32_t d) {
+  return (275 * m) / 9 - (leap ? 1 : 2) * ((m + 9) / 12) + d - 30;
+}
+
+// CAPF_OP_TEMPORAL_FIELD on a non-NULL DATE / LOCALDATETIME
+__device__ inline int64_t temporal_field(const Val &a, int32_t field) {
+  int32_t z;
+  int64_t tod = 0;  // microseconds into the day
+  if (a.t == CAPF_TYPE_LOCALDATETIME) {
+    const int64_t day = floor_div64(a.b, MICROS_PER_DAY);
+    z = (int32_t)day;
+    tod = a.b - day * MICROS_PER_DAY;
+  } else {
+    z = (int32_t)a.b;
+  }
+  if (field >= CAPF_TEMPORAL_HOUR) {
+    const uint32_t sod = (uint32_t)(tod / 1000000), us = (uint32_t)(tod - (int64_t)sod * 1000000);
+    switch (field) {
+      case CAPF_TEMPORAL_HOUR: return sod / 3600;
+      case CAPF_TEMPORAL_MINUTE: return sod / 60 % 60;
+      case CAPF_TEMPORAL_SECOND: return sod % 60;
+      case CAPF_TEMPORAL_MILLISECOND: return us / 1000;
+      default: return us;
+    }
+  }
+  const int32_t dow = z + 3 - 7 * floor_div(z + 3, 7) + 1;  // ISO: Monday = 1 (1970-01-01 was a Thursday)
+  if (field == CAPF_TEMPORAL_DAY_OF_WEEK) return dow;
+  const Civil c = civil_from_days(z);
+  switch (field) {
+    case CAPF_TEMPORAL_YEAR: return c.y;
+    case CAPF_TEMPORAL_MONTH: return c.m;
+    case CAPF_TEMPORAL_DAY: return c.d;
+    case CAPF_TEMPORAL_QUARTER: return (c.m - 1) / 3 + 1;
+    default: break;
+  }
+  const bool leap = leap_year(c.y);
+  const int32_t ord = ordinal_day(leap, c.m, c.d);
+  if (field == CAPF_TEMPORAL_ORDINAL_DAY) return ord;
+  if (field == CAPF_TEMPORAL_DAY_OF_QUARTER) return ord - ordinal_day(leap, (c.m - 1) / 3 * 3 + 1, 1) + 1;
+  // ISO week of the week-based year from the ordinal day and the weekday:
+  // week 0 belongs to the previous year's last week (53 when that year began
+  // on a Thursday, or on a Wednesday and was a leap year — told from this
+  // year's January 1st: a Friday, or a Saturday after a leap year); week 53
+  // is week 1 of the next year unless this year has 53 weeks
+  int32_t w = (ord - dow + 10) / 7, wy = c.y;
+  const int32_t jan1 = dow - ord - 7 * floor_div(dow - ord, 7) + 1;  // weekday of January 1st
+  if (w < 1) {
+    wy = c.y - 1;
+    w = (jan1 == 5 || (jan1 == 6 && leap_year(c.y - 1))) ? 53 : 52;
+  } else if (w == 53 && !(jan1 == 4 || (jan1 == 3 && leap))) {
+    wy = c.y + 1;
+    w = 1;
+  }
+  return field == CAPF_TEMPORAL_WEEK ? w : wy;
+}
+
+// CAPF_OP_TEMPORAL_ADD on a non-NULL DATE / LOCALDATETIME: java.time's
+// plusMonths (the day of month clamped to the target month's length), then
+// the microseconds — whole days of them, truncated toward zero, on a DATE
+__device__ inline int64_t temporal_add(const Val &a, int32_t months, int64_t micros) {
+  const bool ldt = a.t == CAPF_TYPE_LOCALDATETIME;
+  int64_t day = a.b, tod = 0;
+  if (ldt) {
+    day = floor_div64(a.b, MICROS_PER_DAY);
+    tod = a.b - day * MICROS_PER_DAY;
+  }
+  if (months != 0) {
+    const Civil c = civil_from_days((int32_t)day);
+    const int32_t total = c.y * 12 + (c.m - 1) + months;  // (|months| <= 2^30: the host verifier)
+    const int32_t ny = floor_div(total, 12), nm = total - ny * 12 + 1;
+    const int32_t len = nm == 2 ? (leap_year(ny) ? 29 : 28) : 30 + ((nm + (nm >> 3)) & 1);
+    day = days_from_civil(ny, nm, c.d < len ? c.d : len);
+  }
+  return ldt ? day * MICROS_PER_DAY + tod + micros : day + micros / MICROS_PER_DAY;
 }
 
 constexpr int MAX_STACK = 24;
@@ -1293,6 +1413,18 @@ __device__ Val run_program(const Instr *code, int ncode, const ColView *cols, in
         }
         break;
       }
+      case OP_LIT_TEMPORAL: st[sp++] = mk(in.i, (int32_t)in.f, 0); break;
+      case OP_TEMPORAL_FIELD: {  // in.i = the field (CAPF_TEMPORAL_*); the operand's type says DATE or LOCALDATETIME
+        Val a = st[--sp];
+        st[sp++] = a.nul ? mknull(CAPF_TYPE_INT64) : mk(temporal_field(a, (int32_t)in.i), CAPF_TYPE_INT64, 0);
+        break;
+      }
+      case OP_TEMPORAL_ADD: {  // in.f = months, in.i = microseconds
+        Val a = st[--sp];
+        if (!a.nul) a.b = temporal_add(a, (int32_t)in.f, in.i);
+        st[sp++] = a;
+        break;
+      }
       default:
         if constexpr (LAM) {  // CAPF_OP_LAMBDA: lambda slot in.i
           if (in.op == OP_LAMBDA) {
@@ -1474,11 +1606,12 @@ static DeviceProgram upload_program(Session *s, const Program &p,
   for (auto &in : code) {
     switch (in.op) {
       case OP_COL: case OP_LIT_INT: case OP_LIT_FLOAT: case OP_LIT_BOOL: case OP_LIT_STRING:
-      case OP_LIT_NULL: case OP_LIST_SIZE: case OP_RAND: case OP_LAMBDA: depth++; break;
+      case OP_LIT_NULL: case OP_LIST_SIZE: case OP_RAND: case OP_LAMBDA: case OP_LIT_TEMPORAL: depth++; break;
       case OP_AND: case OP_OR: case OP_COALESCE: depth -= (int)in.i - 1; break;
       case OP_NOT: case OP_IS_NULL: case OP_IS_NOT_NULL: case OP_NEG: case OP_TO_FLOAT:
       case OP_TO_INTEGER: case OP_STR_LEN: case OP_TO_BOOLEAN: case OP_IN_SET: case OP_STR_MAP:
-      case OP_STR_TO_NUM: case OP_LIST_INDEX: case OP_STR_RANK: case OP_IN_LIST: break;
+      case OP_STR_TO_NUM: case OP_LIST_INDEX: case OP_STR_RANK: case OP_IN_LIST:
+      case OP_TEMPORAL_FIELD: case OP_TEMPORAL_ADD: break;
       case OP_IF: depth -= 2; break;
       case OP_STR_MATCH: depth -= 1; break;  // pattern and subject in, a BOOLEAN out
       case OP_VALUE_MAP: depth -= in.f != 0.0 ? 1 : 0; break;
@@ -1519,7 +1652,8 @@ ColPtr eval_program(Session *s, const Program &p, const std::vector<std::string>
     const bool lit = (in.op == OP_LIT_BOOL && out_type == Type::Bool) ||
                      (in.op == OP_LIT_INT && out_type == Type::Int64) ||
                      (in.op == OP_LIT_FLOAT && out_type == Type::Float64) ||
-                     (in.op == OP_LIT_STRING && out_type == Type::String);
+                     (in.op == OP_LIT_STRING && out_type == Type::String) ||
+                     (in.op == OP_LIT_TEMPORAL && is_temporal(out_type) && in.f == (double)(int32_t)out_type);
     if (lit) {
       Column proto;
       proto.type = out_type;
@@ -1722,7 +1856,9 @@ static bool program_nullable(const Program &p, const std::vector<std::string> &n
   };
   for (auto &in : p.code) {
     switch (in.op) {
-      case OP_LIT_INT: case OP_LIT_FLOAT: case OP_LIT_BOOL: case OP_LIT_STRING: st.push_back(0); break;
+      case OP_LIT_INT: case OP_LIT_FLOAT: case OP_LIT_BOOL: case OP_LIT_STRING: case OP_LIT_TEMPORAL:
+        st.push_back(0);
+        break;
       case OP_LAMBDA: st.push_back(elem_nullable || in.i != 0); break;
       case OP_COL: {
         // (a lazy gather has no validity of its own until it is forced: its index and its source say)
@@ -1741,7 +1877,7 @@ static bool program_nullable(const Program &p, const std::vector<std::string> &n
         st.push_back(a || b);
         break;
       }
-      case OP_NOT: case OP_NEG: break;
+      case OP_NOT: case OP_NEG: case OP_TEMPORAL_FIELD: case OP_TEMPORAL_ADD: break;  // NULL in, NULL out
       case OP_IS_NULL: case OP_IS_NOT_NULL: pop(); st.push_back(0); break;
       default: return true;
     }
@@ -1946,6 +2082,12 @@ static bool ft_operand(const Instr &in, const std::vector<std::string> &pnames,
     t = Type::Int64;
     return true;
   }
+  if (in.op == OP_LIT_TEMPORAL) {  // a DATE / LOCALDATETIME literal: an int64 of its type
+    o.is_lit = 1;
+    o.lit = in.i;
+    t = (Type)(int32_t)in.f;
+    return is_temporal(t);
+  }
   if (in.op != OP_COL || in.i < 0 || (size_t)in.i >= pnames.size()) return false;
   int idx = -1;
   for (size_t k = 0; k < names.size(); ++k)
@@ -1953,7 +2095,7 @@ static bool ft_operand(const Instr &in, const std::vector<std::string> &pnames,
   if (idx < 0) return false;
   const ColPtr &c = d.cols[(size_t)idx];
   t = c->type;
-  if (t != Type::Int64 && t != Type::String && t != Type::Bool) return false;
+  if (!is_int_payload(t) && t != Type::String && t != Type::Bool) return false;
   std::shared_ptr<LazyGather> lz;
   {
     std::lock_guard<std::mutex> g(c->mu);
@@ -1994,7 +2136,7 @@ bool ft_compile(const Program &p, const std::vector<std::string> &names, const D
                                       op == OP_GT || op == OP_GE))
       return false;
     if (ta != tb) return false;  // mixed types: the interpreter's rules
-    if (ta != Type::Int64 && op != OP_EQ && op != OP_NEQ) return false;
+    if (!is_int_payload(ta) && op != OP_EQ && op != OP_NEQ) return false;
     t.op = op;
     pc += 3;
     t.neg = 0;

@@ -32,6 +32,8 @@ const char *type_name(Type t) {
     case Type::Bool: return "BOOLEAN";
     case Type::String: return "STRING";
     case Type::List: return "LIST";
+    case Type::Date: return "DATE";
+    case Type::LocalDateTime: return "LOCALDATETIME";
   }
   return "?";
 }
@@ -218,6 +220,11 @@ Type infer_type(const Program &p, const std::vector<std::string> &names,
     st.pop_back();
     return t;
   };
+  // a DATE / LOCALDATETIME takes comparison with its own type, IS [NOT] NULL,
+  // COALESCE, IF, IN, its accessors and + duration: nothing numeric
+  auto no_temporal = [&](Type t, const char *what) {
+    if (is_temporal(t)) illegal(std::string(what) + " of a " + type_name(t) + " value");
+  };
   for (auto &in : p.code) {
     switch (in.op) {
       case OP_COL: {
@@ -239,9 +246,36 @@ Type infer_type(const Program &p, const std::vector<std::string> &names,
       case OP_LIT_FLOAT: st.push_back(Type::Float64); break;
       case OP_LIT_BOOL: st.push_back(Type::Bool); break;
       case OP_LIT_STRING: st.push_back(Type::String); break;
+      case OP_LIT_TEMPORAL: {
+        const Type t = in.f == (double)CAPF_TYPE_DATE            ? Type::Date
+                       : in.f == (double)CAPF_TYPE_LOCALDATETIME ? Type::LocalDateTime
+                                                                 : Type::Null;
+        if (t == Type::Null) illegal("a temporal literal must be typed DATE or LOCALDATETIME");
+        st.push_back(t);
+        break;
+      }
+      case OP_TEMPORAL_FIELD: {
+        Type a = pop();
+        if (a != Type::Null && !is_temporal(a))
+          illegal(std::string("a temporal accessor on ") + type_name(a));
+        if (in.i < CAPF_TEMPORAL_YEAR || in.i > CAPF_TEMPORAL_MICROSECOND) illegal("temporal field out of range");
+        if (a == Type::Date && in.i >= CAPF_TEMPORAL_HOUR) illegal("a time accessor on a DATE");
+        st.push_back(Type::Int64);
+        break;
+      }
+      case OP_TEMPORAL_ADD: {
+        Type a = pop();
+        if (a != Type::Null && !is_temporal(a))
+          illegal(std::string("a duration added to ") + type_name(a));
+        // (the kernel adds the months to 12 · year in 32 bits)
+        if (!(in.f >= -1073741824.0 && in.f <= 1073741824.0) || in.f != (double)(int64_t)in.f)
+          illegal("duration months out of range");
+        st.push_back(a);
+        break;
+      }
       case OP_LIT_NULL: {
         Type t = (Type)in.i;
-        if (in.i < 0 || in.i > 4) t = Type::Null;
+        if (in.i < 0 || (in.i > 4 && !is_temporal(t))) t = Type::Null;
         st.push_back(t);
         break;
       }
@@ -267,6 +301,8 @@ Type infer_type(const Program &p, const std::vector<std::string> &names,
       case OP_IS_NULL: case OP_IS_NOT_NULL: pop(); st.push_back(Type::Bool); break;
       case OP_ADD: case OP_SUB: case OP_MUL: case OP_DIV: case OP_MOD: {
         Type b = pop(), a = pop();
+        no_temporal(a, "arithmetic");
+        no_temporal(b, "arithmetic");
         if ((a != Type::Null && !is_numeric(a)) || (b != Type::Null && !is_numeric(b)))
           not_impl(std::string("arithmetic on ") + type_name(a) + " and " + type_name(b));
         if (a == Type::Float64 || b == Type::Float64)
@@ -279,18 +315,21 @@ Type infer_type(const Program &p, const std::vector<std::string> &names,
       }
       case OP_NEG: {
         Type a = pop();
+        no_temporal(a, "negation");
         if (a != Type::Null && !is_numeric(a)) not_impl("negation of non-numeric");
         st.push_back(a);
         break;
       }
       case OP_TO_FLOAT: {
         Type a = pop();
+        no_temporal(a, "toFloat");
         if (a == Type::String) not_impl("toFloat on strings");
         st.push_back(Type::Float64);
         break;
       }
       case OP_TO_INTEGER: {
         Type a = pop();
+        no_temporal(a, "toInteger");
         if (a == Type::String) not_impl("toInteger on strings");
         st.push_back(Type::Int64);
         break;
@@ -317,7 +356,7 @@ Type infer_type(const Program &p, const std::vector<std::string> &names,
         if (in.i < 0 || (size_t)in.i >= p.names.size() || !is_literal_set_name(p.names[in.i]))
           illegal("malformed expression program (literal set)");
         Type a = pop();
-        if (a != Type::Int64 && a != Type::String && a != Type::Null) illegal("IN set over a non-integer value");
+        if (!is_int_payload(a) && a != Type::String && a != Type::Null) illegal("IN set over a non-integer value");
         st.push_back(Type::Bool);
         break;
       }
@@ -382,6 +421,7 @@ Type infer_type(const Program &p, const std::vector<std::string> &names,
       case OP_LOG: case OP_LOG10: case OP_EXP: case OP_SIN: case OP_COS: case OP_TAN:
       case OP_ASIN: case OP_ACOS: case OP_ATAN: case OP_DEGREES: case OP_RADIANS: {
         Type a = pop();
+        no_temporal(a, "a math function");
         if (a != Type::Null && !is_numeric(a)) not_impl(std::string("math function on ") + type_name(a));
         const bool keeps = in.op == OP_ABS || in.op == OP_CEIL || in.op == OP_FLOOR || in.op == OP_SIGN;
         st.push_back(keeps && a == Type::Int64 ? Type::Int64 : Type::Float64);
@@ -389,6 +429,8 @@ Type infer_type(const Program &p, const std::vector<std::string> &names,
       }
       case OP_ATAN2: {
         Type b = pop(), a = pop();
+        no_temporal(a, "atan2");
+        no_temporal(b, "atan2");
         if ((a != Type::Null && !is_numeric(a)) || (b != Type::Null && !is_numeric(b)))
           not_impl("atan2 of non-numeric values");
         st.push_back(Type::Float64);
@@ -396,6 +438,7 @@ Type infer_type(const Program &p, const std::vector<std::string> &names,
       }
       case OP_TO_BOOLEAN: {
         Type a = pop();
+        no_temporal(a, "toBoolean");
         if (a != Type::Null && a != Type::Bool && a != Type::String)
           not_impl(std::string("toBoolean on ") + type_name(a));
         st.push_back(Type::Bool);
@@ -1159,7 +1202,7 @@ static capf_status table_from(capf_session *cs, int32_t ncols, const char *const
   d->nrows = nrows;
   for (int i = 0; i < ncols; ++i) {
     Type t = (Type)types[i];
-    if (types[i] < 0 || types[i] > 4) illegal("bad column type");
+    if (types[i] < 0 || (types[i] > 4 && !is_temporal((Type)types[i]))) illegal("bad column type");
     n->names.emplace_back(names[i]);
     n->types.push_back(t);
     auto c = std::make_shared<Column>();
@@ -1414,7 +1457,7 @@ capf_status capf_table_column_range(capf_table *t, const char *col, int64_t *mn,
   need(mx, "max");
   need(non_null, "non_null");
   int i = t->node->col_index_or_throw(col);
-  if (t->node->types[i] != Type::Int64 && t->node->types[i] != Type::String)
+  if (!is_int_payload(t->node->types[i]) && t->node->types[i] != Type::String)
     illegal("column range: INTEGER or STRING columns only");
   DataPtr d = materialize(t->node);
   force(d->cols[i]);
@@ -1429,7 +1472,7 @@ static void check_wire(Type t, int32_t width, int64_t base) {
   const bool ok = t == Type::Null     ? width == 0
                   : t == Type::Bool   ? width == 1
                   : t == Type::Float64 ? width == 8 && base == 0
-                  : (t == Type::Int64 || t == Type::String) ? (width == 3 || width == 4 || (width == 8 && base == 0))
+                  : (is_int_payload(t) || t == Type::String) ? (width == 3 || width == 4 || (width == 8 && base == 0))
                                                            : false;
   if (!ok) illegal(std::string("packed rows: width ") + std::to_string(width) + " does not fit a " + type_name(t) +
                    " column");
@@ -2086,6 +2129,11 @@ capf_status capf_table_group_ex(capf_table *t, int32_t n_by, const char *const *
       a.arg = Program::from_c(&agg_args[i]);
       Type at = infer_type(a.arg, c->names, c->types);
       if (at == Type::List) not_impl("aggregation of list values");
+      if (is_temporal(at)) {  // ordered and countable, nothing else (no duration type to hold a sum)
+        if (a.kind == CAPF_AGG_COLLECT) not_impl(std::string("collect of ") + type_name(at) + " values");
+        if (a.kind != CAPF_AGG_COUNT && a.kind != CAPF_AGG_MIN && a.kind != CAPF_AGG_MAX)
+          illegal(std::string("sum / avg / stDev / percentile of ") + type_name(at) + " values");
+      }
       switch (a.kind) {
         case CAPF_AGG_COUNT: a.out_type = Type::Int64; break;
         case CAPF_AGG_SUM:
@@ -2163,7 +2211,7 @@ capf_status capf_table_explode_values(capf_table *t, const char *name, int32_t t
   need(name, "name");
   need(out, "out");
   if (n < 0) illegal("negative list length");
-  if (type < CAPF_TYPE_NULL || type > CAPF_TYPE_STRING) illegal("bad list element type");
+  if (type < CAPF_TYPE_NULL || (type > CAPF_TYPE_STRING && !is_temporal((Type)type))) illegal("bad list element type");
   const NodePtr &c = t->node;
   if (c->col_index(name) >= 0) illegal(std::string("column '") + name + "' already exists");
   Type ty = (Type)type;
@@ -2294,6 +2342,7 @@ capf_status capf_table_list_columns(capf_table *t, int32_t n, const char *const 
     const int idx = c->col_index_or_throw(cols[j]);
     const Type ct = c->types[(size_t)idx];
     if (ct == Type::List) not_impl("nested lists");
+    if (is_temporal(ct)) not_impl(std::string("a list of ") + type_name(ct) + " elements");
     // a NULL-typed item is a NULL element: the element type is that of the
     // other items (Type::Null when there are none)
     if (ct == Type::Null || et == Type::Null || et == ct) et = ct == Type::Null ? et : ct;
@@ -2356,6 +2405,7 @@ capf_status capf_table_list_fn(capf_table *t, int32_t fn, int32_t nargs, const c
     for (int j = 0; j < 2; ++j) {
       const Type ct = type_of(j) == Type::List ? list_elem_of(c, nn->name_cols[(size_t)j]) : type_of(j);
       if (ct == Type::List) not_impl("nested lists");
+      if (is_temporal(ct)) not_impl(std::string("a list of ") + type_name(ct) + " elements");
       if (ct == Type::Null || et == Type::Null || et == ct) et = ct == Type::Null ? et : ct;
       else if ((et == Type::Int64 || et == Type::Float64) && (ct == Type::Int64 || ct == Type::Float64))
         et = Type::Float64;  // INTEGER and FLOAT elements widen together
@@ -2420,6 +2470,7 @@ capf_status capf_table_list_lambda(capf_table *t, int32_t kind, const char *list
   need(name, "name");
   need(out, "out");
   if (kind < CAPF_LAMBDA_COMPREHENSION || kind > CAPF_LAMBDA_REDUCE) illegal("unknown lambda expression kind");
+  if (is_temporal((Type)out_type)) not_impl(std::string("a lambda expression that gives ") + type_name((Type)out_type) + " values");
   if (out_type < 0 || out_type > 4) illegal("lambda expression result type out of range");
   const bool quant = kind >= CAPF_LAMBDA_ANY && kind <= CAPF_LAMBDA_SINGLE, reduce = kind == CAPF_LAMBDA_REDUCE;
   if (quant && !pred) illegal("any / all / none / single need a predicate");

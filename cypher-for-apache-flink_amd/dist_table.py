@@ -129,7 +129,7 @@ class GpuExchange:
         cols = table.physicalColumns
         types = [table.capf_type(c) for c in cols]
         if any(t not in (0, 1, 2, 3, 4) for t in types):
-            raise _lib.NotImplementedException("LIST columns are not moved between ranks")
+            raise _lib.NotImplementedException("LIST, DATE and LOCALDATETIME columns are not moved between ranks")
         k = len(cols)
         has, lo, hi = [], [], []
         big = (1 << 63) - 1

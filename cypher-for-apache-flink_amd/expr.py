@@ -19,15 +19,22 @@ from typing import Tuple
 
 # capf column types (include/capf_gpu.h)
 T_NULL, T_INT, T_FLOAT, T_BOOL, T_STRING, T_LIST = 0, 1, 2, 3, 4, 5
+# CTDate / CTLocalDateTime: int64 days / microseconds since the epoch (temporal.py)
+T_DATE, T_LOCALDATETIME = 6, 7
+T_TEMPORAL = (T_DATE, T_LOCALDATETIME)
+# CTDuration: a static type of the host only — there is no duration column
+# (a duration folds away, or is the immediate of CAPF_OP_TEMPORAL_ADD)
+T_DURATION = -2
 
 CT_TO_CAPF = {
     "NULL": T_NULL, "INTEGER": T_INT, "FLOAT": T_FLOAT, "BOOLEAN": T_BOOL, "STRING": T_STRING,
     "NODE": T_INT, "RELATIONSHIP": T_INT, "ANY": T_NULL,
     # CTList properties (LIST columns: int64 offsets + an element column)
     "LIST(INTEGER)": T_LIST, "LIST(FLOAT)": T_LIST, "LIST(BOOLEAN)": T_LIST, "LIST(STRING)": T_LIST,
+    "DATE": T_DATE, "LOCALDATETIME": T_LOCALDATETIME,
 }
 CAPF_TO_CT = {T_NULL: "NULL", T_INT: "INTEGER", T_FLOAT: "FLOAT", T_BOOL: "BOOLEAN", T_STRING: "STRING",
-              T_LIST: "LIST"}
+              T_LIST: "LIST", T_DATE: "DATE", T_LOCALDATETIME: "LOCALDATETIME"}
 
 # opcodes
 OP_COL, OP_LIT_INT, OP_LIT_FLOAT, OP_LIT_BOOL, OP_LIT_STRING, OP_LIT_NULL = 1, 2, 3, 4, 5, 6
@@ -41,6 +48,15 @@ OP_SIN, OP_COS, OP_TAN, OP_ASIN, OP_ACOS, OP_ATAN, OP_DEGREES, OP_RADIANS = 79, 
 OP_ATAN2, OP_TO_BOOLEAN, OP_IN_SET, OP_STR_MAP, OP_VALUE_MAP = 87, 88, 89, 90, 91
 OP_STR_TO_NUM, OP_RAND, OP_LIST_INDEX, OP_STR_RANK, OP_STR_MATCH, OP_IN_LIST = 92, 93, 94, 95, 96, 97
 OP_LAMBDA = 98  # push lambda slot iarg (only inside the programs of capf_table_list_lambda)
+# a DATE / LOCALDATETIME literal (iarg = payload, farg = type); d.field (iarg = CAPF_TEMPORAL_*);
+# temporal + duration (iarg = microseconds, farg = months)
+OP_LIT_TEMPORAL, OP_TEMPORAL_FIELD, OP_TEMPORAL_ADD = 99, 100, 101
+# CAPF_TEMPORAL_*: accessor name (lower case, TemporalConversions.scala:155-173) -> field id;
+# ids from TEMPORAL_HOUR on exist on a LOCALDATETIME only
+TEMPORAL_FIELDS = {"year": 0, "quarter": 1, "month": 2, "week": 3, "weekyear": 4, "dayofquarter": 5, "day": 6,
+                   "ordinalday": 7, "dayofweek": 8, "weekday": 8, "hour": 9, "minute": 10, "second": 11,
+                   "millisecond": 12, "microsecond": 13}
+TEMPORAL_HOUR = 9
 NARY_CHUNK = 8   # operands AND / OR / COALESCE take per instruction (longer ones fold in chunks)
 IN_SET_MIN = 17  # list length from which IN runs as a session-set lookup (shorter: an OR of equalities)
 
@@ -932,6 +948,137 @@ class MapExpression(Expr):
         return "{" + ", ".join(f"{k}: {v}" for k, v in self.items) + "}"
 
 
+# Temporal values (okapi Expr.scala:487-507, 544-548, 573-575, 1258-1277; the
+# Morpheus lowering SparkSQLExprMapper.scala:153-159, 186-191).  A constructor's
+# argument is resolved when the program is compiled (`temporal_argument`):
+# date / localdatetime become typed literals (CAPF_OP_LIT_TEMPORAL), their
+# accessors CAPF_OP_TEMPORAL_FIELD, temporal ± duration CAPF_OP_TEMPORAL_ADD.
+# A duration has no column type: its accessors and duration ± duration fold on
+# the host (`duration_value`), and anywhere but beside a temporal in + / − it
+# is NotImplemented.
+@dataclass(frozen=True)
+class Date(Expr):
+    """date([arg]) (okapi Date, Expr.scala:1270): a string, a map of integer /
+    string values or NULL; without an argument the current date."""
+    arg: Expr = None
+
+    def __str__(self):
+        return f"date({'' if self.arg is None else self.arg})"
+
+
+@dataclass(frozen=True)
+class LocalDateTime(Expr):
+    """localdatetime([arg]) (okapi LocalDateTime, Expr.scala:1268)."""
+    arg: Expr = None
+
+    def __str__(self):
+        return f"localdatetime({'' if self.arg is None else self.arg})"
+
+
+@dataclass(frozen=True)
+class Duration(Expr):
+    """duration(arg) (okapi Duration, Expr.scala:1272-1277)."""
+    arg: Expr
+
+    def __str__(self):
+        return f"duration({self.arg})"
+
+
+@dataclass(frozen=True)
+class TemporalProperty(Expr):
+    """e.key of a DATE, LOCALDATETIME or DURATION value (okapi DateProperty /
+    LocalDateTimeProperty / DurationProperty, Expr.scala:487-507): an INTEGER.
+    The lowering dispatches on the static type of the owner, so the three
+    classes differ in name only."""
+    expr: Expr
+    key: str
+
+    def __str__(self):
+        return f"{self.expr}.{self.key}"
+
+
+@dataclass(frozen=True)
+class DateProperty(TemporalProperty):
+    pass
+
+
+@dataclass(frozen=True)
+class LocalDateTimeProperty(TemporalProperty):
+    pass
+
+
+@dataclass(frozen=True)
+class DurationProperty(TemporalProperty):
+    pass
+
+
+def temporal_argument(arg, params):
+    """resolveTemporalArgument (TemporalConversions.scala:123-151): None for
+    NULL, the string, or the {key: int} map of a constructor's argument."""
+    from ._lib import IllegalArgumentException, NotImplementedException
+
+    def scalar(x, what):
+        if isinstance(x, Param):
+            x = (params or {}).get(x.pname)
+        elif isinstance(x, (StringLit, IntegerLit)):
+            x = x.v
+        else:
+            raise NotImplementedException(
+                f"Parsing temporal values is currently only supported for Literal-Maps, got {what}")
+        return x
+
+    if isinstance(arg, NullLit):
+        return None
+    if isinstance(arg, MapExpression):
+        out = {}
+        for k, x in arg.items:
+            v = scalar(x, f"{k} -> {x}")
+            if isinstance(v, bool) or not isinstance(v, (int, str)):
+                raise IllegalArgumentException(f"A map value of type CypherString or CypherInteger, got {v!r}")
+            try:
+                out[k] = int(v)
+            except ValueError:
+                raise IllegalArgumentException(f"A map value that is an integer, got {v!r}") from None
+        return out
+    if isinstance(arg, (StringLit, Param)):
+        v = arg.v if isinstance(arg, StringLit) else (params or {}).get(arg.pname)
+        if not isinstance(v, str):
+            raise IllegalArgumentException(f"Parameter `{arg}` to be a CypherString, got {v!r}")
+        return v
+    raise NotImplementedException(
+        f"Parsing temporal values is currently only supported for Literal-Maps and String literals, got {arg}")
+
+
+def temporal_value(e, params=None):
+    """The datetime.date / datetime.datetime of a Date / LocalDateTime
+    constructor (None: NULL); no argument reads the clock."""
+    import datetime
+
+    from . import temporal
+    if e.arg is None:
+        return datetime.datetime.now() if isinstance(e, LocalDateTime) else datetime.date.today()
+    a = temporal_argument(e.arg, params)
+    if a is None:
+        return None
+    return temporal.parse_local_datetime(a) if isinstance(e, LocalDateTime) else temporal.parse_date(a)
+
+
+def duration_value(e, params=None):
+    """(True, DurationValue or None for NULL) of a duration-valued expression —
+    duration(arg), or + / − of two such — else (False, None)."""
+    from . import temporal
+    if isinstance(e, Duration):
+        a = temporal_argument(e.arg, params)
+        return True, (None if a is None else temporal.parse_duration(a))
+    if type(e).__name__ in ("Add", "Subtract"):
+        (oa, a), (ob, b) = duration_value(e.lhs, params), duration_value(e.rhs, params)
+        if oa and ob:
+            if a is None or b is None:
+                return True, None
+            return True, (a + b if type(e).__name__ == "Add" else a - b)
+    return False, None
+
+
 # properties(x) (okapi Properties, Expr.scala:851; FlinkSQLExprMapper.scala:167-177):
 # the MAP of a node's / relationship's property columns (every key of its
 # header, NULL values included), or a MAP itself
@@ -1090,6 +1237,12 @@ def _value_type(v):
         return T_FLOAT
     if isinstance(v, str):
         return T_STRING
+    if type(v).__module__ == "datetime":  # (datetime first: it is a subclass of date)
+        import datetime
+        if isinstance(v, datetime.datetime):
+            return T_LOCALDATETIME
+        if isinstance(v, datetime.date):
+            return T_DATE
     return None
 
 
@@ -1128,6 +1281,8 @@ def list_values(e, params):
                 out.append(x.v)
             elif isinstance(x, Param):
                 out.append((params or {}).get(x.pname))
+            elif isinstance(x, (Date, LocalDateTime)):  # resolved here: a datetime.date / datetime value
+                out.append(temporal_value(x, params))
             else:
                 return None
         return out
@@ -1393,8 +1548,12 @@ def _static_type(e, header, columns, params=None, coltype=None):
         return T_FLOAT
     if type(e).__name__ in ("Labels", "Keys") and isinstance(e.expr, NullLit):
         return T_NULL
-    if isinstance(e, (ToInteger, Size, Id)):
+    if isinstance(e, (ToInteger, Size, Id, TemporalProperty)):
         return T_INT
+    if isinstance(e, (Date, LocalDateTime)):
+        return T_LOCALDATETIME if isinstance(e, LocalDateTime) else T_DATE
+    if isinstance(e, Duration):
+        return T_DURATION
     if isinstance(e, ToBoolean) or type(e).__name__ == "RegexMatch" or type(e).__name__ in _STR_MATCH:
         return T_BOOL
     if type(e).__name__ in _STR_FUNCS or isinstance(e, (Substring, Replace, ToString)):
@@ -1431,6 +1590,12 @@ def _static_type(e, header, columns, params=None, coltype=None):
                     return T_LIST
         if name == "Add" and T_STRING in (ta, tb):
             return T_STRING
+        if name in ("Add", "Subtract") and T_DURATION in (ta, tb):  # (Expr.scala:544-548)
+            if ta == tb:
+                return T_DURATION
+            if ta in T_TEMPORAL or (name == "Add" and tb in T_TEMPORAL):
+                return ta if ta in T_TEMPORAL else tb
+            return None
         if ta in (T_INT, T_FLOAT) and tb in (T_INT, T_FLOAT):
             return T_FLOAT if T_FLOAT in (ta, tb) else T_INT
         return None
@@ -1481,6 +1646,9 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
             if intern is None:
                 raise ValueError("string literal without a string dictionary")
             emit(OP_LIT_STRING, intern(v))
+        elif _value_type(v) in T_TEMPORAL:
+            from .temporal import temporal_payload
+            emit(OP_LIT_TEMPORAL, temporal_payload(v), _value_type(v))
         else:
             from ._lib import NotImplementedException
             raise NotImplementedException(f"literal {v!r} of type {type(v).__name__}")
@@ -1559,6 +1727,80 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
     def not_impl(what):
         from ._lib import NotImplementedException
         raise NotImplementedException(f"No support for converting Cypher expression {what} to a GPU expression")
+
+    def type_name(t):
+        return CAPF_TO_CT.get(t, "DURATION" if t == T_DURATION else "ANY")
+
+    def duration_not_impl(e):
+        from ._lib import NotImplementedException
+        raise NotImplementedException(
+            f"a DURATION value is supported only as the operand of temporal + / - duration and under its "
+            f"accessors, where it folds away (there is no DURATION column): {e}")
+
+    def temporal_property(e):
+        """d.year / ldt.hour (CAPF_OP_TEMPORAL_FIELD; names case-insensitive,
+        TemporalConversions.scala:155-173) or an accessor of a duration, which
+        folds to an INTEGER literal (TemporalUdfs.scala:115-150)."""
+        from ._lib import IllegalArgumentException, UnsupportedOperationException
+        from .temporal import DURATION_ACCESSORS
+        isd, dv = duration_value(e.expr, params)
+        t = T_DURATION if isd else static_type(e.expr)
+        key = e.key.lower()
+        if t == T_DURATION:
+            if not isd:
+                duration_not_impl(e.expr)
+            if key not in DURATION_ACCESSORS:
+                raise UnsupportedOperationException(f"Unknown Duration accessor: {e.key}")
+            if dv is None:
+                emit(OP_LIT_NULL, T_INT)
+            else:
+                emit(OP_LIT_INT, dv.accessor(key))
+            return
+        if t not in T_TEMPORAL and t != T_NULL:
+            raise IllegalArgumentException(f"{e}: the accessor of a {type_name(t)} value, not a temporal one")
+        fid = TEMPORAL_FIELDS.get(key)
+        if fid is None:
+            raise UnsupportedOperationException(f"Unknown Temporal Accessor: {e.key}")
+        if t == T_DATE and fid >= TEMPORAL_HOUR:
+            raise UnsupportedOperationException(f"Time Accessor '{e.key}' is not supported for a DATE: {e}")
+        if t == T_NULL:
+            emit(OP_LIT_NULL, T_INT)
+            return
+        go(e.expr)
+        emit(OP_TEMPORAL_FIELD, fid)
+
+    def temporal_arith(e, cls):
+        """temporal ± duration and duration + temporal (Expr.scala:544-548):
+        CAPF_OP_TEMPORAL_ADD with the duration's (months, microseconds) as
+        immediates — subtraction negates both.  A duration result, or any other
+        partner of a temporal or a duration, has no lowering."""
+        from ._lib import IllegalArgumentException
+        ta, tb = static_type(e.lhs), static_type(e.rhs)
+        if ta == T_DURATION and tb == T_DURATION:
+            duration_value(e, params)  # (a malformed argument is reported first)
+            duration_not_impl(e)
+        if ta in T_TEMPORAL and tb == T_DURATION:
+            x, d, t = e.lhs, e.rhs, ta
+        elif cls == "Add" and ta == T_DURATION and tb in T_TEMPORAL:
+            x, d, t = e.rhs, e.lhs, tb
+        else:
+            raise IllegalArgumentException(
+                f"{e}: {type_name(ta)} {'+' if cls == 'Add' else '-'} {type_name(tb)} (a DATE or LOCALDATETIME "
+                f"takes + / - with a DURATION only)")
+        isd, dv = duration_value(d, params)
+        if not isd:
+            duration_not_impl(d)
+        if dv is None:
+            emit(OP_LIT_NULL, t)
+            return
+        months, micros = dv.interval
+        sign = 1 if cls == "Add" else -1
+        go(x)
+        emit(OP_TEMPORAL_ADD, sign * micros, sign * months)
+
+    def is_temporal_arith(e):
+        tt = T_TEMPORAL + (T_DURATION,)
+        return static_type(e.lhs) in tt or static_type(e.rhs) in tt
 
     def container_index(e):
         """xs[i] (FlinkSQLExprMapper.scala:262-269), Cypher's 0-based indexing:
@@ -1664,6 +1906,21 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
             emit(OP_LIT_NULL, CT_TO_CAPF.get(e.ctype, T_NULL))
         elif isinstance(e, Param):
             lit(params[e.pname])
+        elif isinstance(e, (Date, LocalDateTime)):
+            if e.arg is None:
+                no_memo()  # the clock, read once per compilation
+            v = temporal_value(e, params)
+            if v is None:
+                emit(OP_LIT_NULL, T_LOCALDATETIME if isinstance(e, LocalDateTime) else T_DATE)
+            else:
+                lit(v)
+        elif isinstance(e, Duration):
+            duration_value(e, params)  # (a malformed argument is reported first)
+            duration_not_impl(e)
+        elif isinstance(e, TemporalProperty):
+            temporal_property(e)
+        elif cls in ("Add", "Subtract") and is_temporal_arith(e):
+            temporal_arith(e, cls)
         elif cls in ("Head", "Last"):  # xs[0] / xs[-1] (SparkSQLExprMapper.scala:167-168)
             container_index(ContainerIndex(e.expr, IntegerLit(0 if cls == "Head" else -1)))
         elif cls == "Add" and static_type(e) == T_LIST:
@@ -1754,7 +2011,12 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
             # operands of incomparable types compare to NULL (Cypher: 1 < 'a'
             # is null, so a WHERE drops the row — PredicateTests.scala:195)
             ta, tb = static_type(e.lhs), static_type(e.rhs)
+            if T_DURATION in (ta, tb):
+                duration_not_impl(e)
             if None not in (ta, tb) and T_NULL not in (ta, tb) and not _comparable(ta, tb):
+                if ta in T_TEMPORAL or tb in T_TEMPORAL:  # (the equality's rule too: the program verifier's)
+                    from ._lib import IllegalArgumentException
+                    raise IllegalArgumentException(f"cannot compare {type_name(ta)} with {type_name(tb)}: {e}")
                 emit(OP_LIT_NULL, T_BOOL)
                 return
             strs = T_STRING in (ta, tb)
@@ -1878,7 +2140,10 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
                 not_impl(e)
             # If(p1, v1, If(p2, v2, … default)): innermost first in postfix
             if e.default is None:
-                emit(OP_LIT_NULL, T_INT)  # expressions.Null(Types.LONG) (:256)
+                # expressions.Null(Types.LONG) (:256); typed as the branches when they are temporal,
+                # which no INTEGER shares a CASE with
+                t = static_type(e)
+                emit(OP_LIT_NULL, t if t in T_TEMPORAL else T_INT)
             else:
                 go(e.default)
             for p, v in reversed(e.alternatives):
@@ -1915,11 +2180,14 @@ def _compile_program(expr, header, columns, params=None, intern=None, coltype=No
                 return
             vals_nn = [v for v in cand if v is not None]
             same = (lt == T_INT and all(_value_type(v) == T_INT for v in vals_nn)) or \
+                (lt in T_TEMPORAL and all(_value_type(v) == lt for v in vals_nn)) or \
                 (lt == T_STRING and intern is not None and all(isinstance(v, str) for v in vals_nn))
             if lset is not None and same and len(cand) >= IN_SET_MIN:
                 # a long list: one binary search per row in a sorted session set
                 # (an element NULL → a miss is NULL, as the OR of equalities gives)
-                codes = tuple(sorted(set(intern(v) if lt == T_STRING else int(v) for v in vals_nn)))
+                from .temporal import temporal_payload
+                codes = tuple(sorted(set(intern(v) if lt == T_STRING else temporal_payload(v) if lt in T_TEMPORAL
+                                         else int(v) for v in vals_nn)))
                 go(e.lhs)
                 emit(OP_IN_SET, name_of(lset(codes)), 1.0 if len(vals_nn) < len(cand) else 0.0)
                 return

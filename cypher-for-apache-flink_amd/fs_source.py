@@ -192,6 +192,9 @@ class FSGraphSource:
     def _read_table(self, path, fields):
         names = [f for f, _ in fields]
         types = [CT_TO_CAPF[_base_type(ct)[0]] for _, ct in fields]
+        if any(_base_type(ct)[0] in ("DATE", "LOCALDATETIME") for _, ct in fields):
+            from ._lib import NotImplementedException
+            raise NotImplementedException(f"{path}: DATE / LOCALDATETIME fields in the CSV source")
         files = self._files(path)
         # The GPU LONG parser rejects an empty field; a nullable field ('INTEGER?')
         # stores NULL as an empty field, so such tables take the host reader.
@@ -261,6 +264,9 @@ def _format_field(v):
         return ""
     if isinstance(v, bool):
         return "true" if v else "false"
+    if type(v).__module__ == "datetime":
+        from ._lib import NotImplementedException
+        raise NotImplementedException(f"DATE / LOCALDATETIME values in the CSV source: {v!r}")
     return str(v)
 
 

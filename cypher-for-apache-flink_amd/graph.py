@@ -35,6 +35,12 @@ class GraphData:
 
 
 def ctype_of(v):
+    if type(v).__module__ == "datetime":  # (datetime first: it is a subclass of date)
+        import datetime
+        if isinstance(v, datetime.datetime):
+            return "LOCALDATETIME"
+        if isinstance(v, datetime.date):
+            return "DATE"
     if isinstance(v, bool):
         return "BOOLEAN"
     if isinstance(v, int):
@@ -48,6 +54,9 @@ def ctype_of(v):
         for x in v:
             if x is not None:
                 et = _join_type(et, ctype_of(x))
+        if et in ("DATE", "LOCALDATETIME"):
+            from ._lib import NotImplementedException
+            raise NotImplementedException(f"LIST property of {et} elements")
         return f"LIST({et or 'INTEGER'})"
     raise NotImplementedError(f"property value {v!r} of type {type(v).__name__}")
 

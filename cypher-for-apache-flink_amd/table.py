@@ -17,12 +17,48 @@ from ctypes import byref, c_char_p, c_double, c_int32, c_int64, c_uint64, c_void
 import numpy as np
 
 from . import _lib
-from .expr import (AGG_COUNT_STAR, CAPF_TO_CT, T_BOOL, T_FLOAT, T_INT, T_LIST, T_NULL, T_STRING, Aggregator,
+from .expr import (AGG_COUNT_STAR, CAPF_TO_CT, T_BOOL, T_DATE, T_FLOAT, T_INT, T_LIST, T_LOCALDATETIME, T_NULL, T_STRING,
+                   T_TEMPORAL, Aggregator,
                    Explode, Var, compile_program, explode_values, may_hold_list_fn, percentile_value)
 
 JOIN_TYPES = {"inner": 0, "left_outer": 1, "right_outer": 2, "full_outer": 3, "cross": 4}
 
-_NP_DTYPE = {T_INT: np.int64, T_FLOAT: np.float64, T_BOOL: np.uint8, T_STRING: np.int64}
+_NP_DTYPE = {T_INT: np.int64, T_FLOAT: np.float64, T_BOOL: np.uint8, T_STRING: np.int64,
+             T_DATE: np.int64, T_LOCALDATETIME: np.int64}
+
+
+def _temporal_array(t, values):
+    """The int64 payloads of a DATE / LOCALDATETIME column: days / microseconds
+    since the epoch from datetime.date / datetime.datetime values (None: 0), an
+    int64 array as it is, or a datetime64 array in the type's unit."""
+    from .temporal import date_to_days, datetime_to_micros
+    if isinstance(values, np.ndarray) and values.dtype != object:
+        if values.dtype.kind == "M":
+            values = values.astype("datetime64[D]" if t == T_DATE else "datetime64[us]")
+        return np.ascontiguousarray(values.astype(np.int64, copy=False))
+    import datetime
+    out = np.zeros(len(values), dtype=np.int64)
+    for i, v in enumerate(values):
+        if v is None:
+            continue
+        if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
+            out[i] = int(v)
+        elif t == T_LOCALDATETIME and isinstance(v, datetime.datetime):
+            out[i] = datetime_to_micros(v)
+        elif t == T_DATE and isinstance(v, datetime.date) and not isinstance(v, datetime.datetime):
+            out[i] = date_to_days(v)
+        else:
+            raise _lib.IllegalArgumentException(f"a {CAPF_TO_CT[t]} column takes "
+                                                f"{'datetime.datetime' if t == T_LOCALDATETIME else 'datetime.date'} "
+                                                f"values, got {v!r}")
+    return out
+
+
+def _temporal_values(t, vals, valid):
+    """datetime.date / datetime.datetime values (None for NULL) of downloaded payloads."""
+    from .temporal import days_to_date, micros_to_datetime
+    conv = days_to_date if t == T_DATE else micros_to_datetime
+    return [conv(v) if ok else None for v, ok in zip(vals.tolist(), valid.tolist())]
 
 
 class GpuSession:
@@ -174,8 +210,12 @@ class GpuSession:
                     vals = np.array([self.intern(v) if v is not None else 0 for v in lst], dtype=np.int64)
                 elif t == T_NULL:
                     vals = None
+                elif t in T_TEMPORAL:
+                    vals = _temporal_array(t, lst)
                 else:
                     vals = np.array([v if v is not None else 0 for v in lst], dtype=_NP_DTYPE[t])
+            elif t in T_TEMPORAL:
+                vals = _temporal_array(t, vals)
             elif t != T_NULL:
                 vals = np.ascontiguousarray(vals.astype(_NP_DTYPE[t], copy=False))
             m = len(values)
@@ -458,6 +498,8 @@ class GpuTable:
         if t == T_LIST:
             return self.list_values(col)
         vals, valid = self.column_arrays(col)
+        if t in T_TEMPORAL:
+            return _temporal_values(t, vals, valid)
         if t not in (T_STRING, T_BOOL) and valid.all():
             return vals.tolist()  # no NULLs: the values as they are
         out = []
@@ -599,6 +641,8 @@ class GpuTable:
                 data = None
             elif t == T_STRING:
                 data = np.array([self.session.intern(v) if v is not None else 0 for v in vals], dtype=np.int64)
+            elif t in T_TEMPORAL:
+                data = _temporal_array(t, vals)
             else:
                 data = np.array([v if v is not None else 0 for v in vals], dtype=_NP_DTYPE[t])
             return self._new("capf_table_explode_values", self._h, col.encode(), int(t), n,

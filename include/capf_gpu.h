@@ -71,7 +71,17 @@ enum {
   CAPF_TYPE_FLOAT64 = 2, /* CTFloat (Types.DOUBLE) */
   CAPF_TYPE_BOOL = 3,    /* CTBoolean, HasLabel / HasType columns */
   CAPF_TYPE_STRING = 4,  /* CTString, stored as int64 dictionary codes */
-  CAPF_TYPE_LIST = 5     /* CTList(elem): the result of collect (see capf_table_list_info) */
+  CAPF_TYPE_LIST = 5,    /* CTList(elem): the result of collect (see capf_table_list_info) */
+  /* CTDate / CTLocalDateTime: an int64 payload like STRING's codes — days since
+   * 1970-01-01 / microseconds since 1970-01-01T00:00:00, negative before the
+   * epoch; no time zone, no nanoseconds (DESIGN.md "Temporal values").  Every
+   * operation that treats a column as plain int64 (upload, download, filter,
+   * union, sort, group / distinct keys, joins on equal-typed keys, MIN / MAX /
+   * COUNT, skip / limit, the FOR encodings) takes them down the INTEGER path and
+   * keeps the type; SUM / AVG / stDev / percentiles are IllegalArgument, collect
+   * and LIST elements NotImplemented.                                         */
+  CAPF_TYPE_DATE = 6,
+  CAPF_TYPE_LOCALDATETIME = 7
 };
 
 /* join types (okapi-relational/.../impl/planning/PhysicalConstants.scala:29-35) */
@@ -257,7 +267,43 @@ enum {
    * Only the programs given to capf_table_list_lambda may hold it: slot 0 is
    * the list element (REDUCE: the accumulator), slot 1 REDUCE's element.
    * Anywhere else it is IllegalArgument.                                      */
-  CAPF_OP_LAMBDA = 98
+  CAPF_OP_LAMBDA = 98,
+  /* A DATE / LOCALDATETIME literal: pushes iarg (days / microseconds since the
+   * epoch) typed farg (CAPF_TYPE_DATE or CAPF_TYPE_LOCALDATETIME).             */
+  CAPF_OP_LIT_TEMPORAL = 99,
+  /* d.year, ldt.hour, ... (okapi DateProperty / LocalDateTimeProperty; the
+   * Morpheus temporalAccessor, TemporalConversions.scala:155-173): pops a DATE
+   * or LOCALDATETIME, pushes field iarg (CAPF_TEMPORAL_*) as an INTEGER; NULL
+   * in, NULL out.  A time field of a DATE is IllegalArgument.                 */
+  CAPF_OP_TEMPORAL_FIELD = 100,
+  /* temporal + duration: pops a DATE or LOCALDATETIME, pushes it moved by farg
+   * months (an integer, exact in a double) and iarg microseconds; NULL in,
+   * NULL out.  The months go first, by java.time's plusMonths (the day of
+   * month clamped to the target month's length).  A DATE then moves by
+   * iarg / 86 400 000 000 days, truncated toward zero (sub-day parts dropped,
+   * TemporalUdfs.scala:46-88); a LOCALDATETIME has its date part moved by the
+   * months and iarg added.  Subtraction is the caller negating both.          */
+  CAPF_OP_TEMPORAL_ADD = 101
+};
+
+/* fields of CAPF_OP_TEMPORAL_FIELD: ISO-8601 calendar (java.time), the week
+ * fields of the week-based year, DAY_OF_WEEK Monday = 1; 0..8 on both types,
+ * 9..13 on a LOCALDATETIME only                                             */
+enum {
+  CAPF_TEMPORAL_YEAR = 0,
+  CAPF_TEMPORAL_QUARTER = 1,
+  CAPF_TEMPORAL_MONTH = 2,
+  CAPF_TEMPORAL_WEEK = 3,
+  CAPF_TEMPORAL_WEEK_YEAR = 4,
+  CAPF_TEMPORAL_DAY_OF_QUARTER = 5,
+  CAPF_TEMPORAL_DAY = 6,
+  CAPF_TEMPORAL_ORDINAL_DAY = 7,
+  CAPF_TEMPORAL_DAY_OF_WEEK = 8,
+  CAPF_TEMPORAL_HOUR = 9,
+  CAPF_TEMPORAL_MINUTE = 10,
+  CAPF_TEMPORAL_SECOND = 11,
+  CAPF_TEMPORAL_MILLISECOND = 12,
+  CAPF_TEMPORAL_MICROSECOND = 13
 };
 
 typedef struct capf_expr {

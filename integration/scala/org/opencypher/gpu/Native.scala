@@ -39,6 +39,9 @@ object Native {
   final val TypeBool = 3
   final val TypeString = 4
   final val TypeList = 5
+  // CTDate / CTLocalDateTime: int64 days / microseconds since 1970-01-01[T00:00:00]
+  final val TypeDate = 6
+  final val TypeLocalDateTime = 7
 
   final val JoinInner = 0
   final val JoinLeftOuter = 1
@@ -69,6 +72,26 @@ object Native {
   final val ListFnRange = 3
   // CAPF_OP_LAMBDA (opcode 98): push lambda slot iarg; only in the programs of capf_table_list_lambda
   final val OpLambda = 98
+  // CAPF_OP_LIT_TEMPORAL (99): a DATE / LOCALDATETIME literal, iarg = payload, farg = type;
+  // CAPF_OP_TEMPORAL_FIELD (100): iarg = CAPF_TEMPORAL_*; CAPF_OP_TEMPORAL_ADD (101): iarg = microseconds,
+  // farg = months.  GpuExprMapper does not lower temporal expressions yet (INTEGRATION.md).
+  final val OpLitTemporal = 99
+  final val OpTemporalField = 100
+  final val OpTemporalAdd = 101
+  final val TemporalYear = 0
+  final val TemporalQuarter = 1
+  final val TemporalMonth = 2
+  final val TemporalWeek = 3
+  final val TemporalWeekYear = 4
+  final val TemporalDayOfQuarter = 5
+  final val TemporalDay = 6
+  final val TemporalOrdinalDay = 7
+  final val TemporalDayOfWeek = 8
+  final val TemporalHour = 9
+  final val TemporalMinute = 10
+  final val TemporalSecond = 11
+  final val TemporalMillisecond = 12
+  final val TemporalMicrosecond = 13
   // CAPF_LAMBDA_* kinds of capf_table_list_lambda
   final val LambdaComprehension = 0
   final val LambdaAny = 1
