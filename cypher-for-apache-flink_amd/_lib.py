@@ -163,6 +163,9 @@ _SIGS = {
                                            c_void_p]),
     "capf_csv_parse_longs": (c_int32, [_S, c_char_p, c_int64, c_char_p, c_int32, _STRS, _PT]),
     "capf_csv_read_longs": (c_int32, [_S, c_char_p, c_char_p, c_int32, _STRS, _PT]),
+    "capf_csv_parse_typed": (c_int32, [_S, c_char_p, c_int64, c_char_p, c_int32, _STRS, POINTER(c_int32), _PT]),
+    "capf_csv_read_typed": (c_int32, [_S, c_char_p, c_char_p, c_int32, _STRS, POINTER(c_int32), _PT]),
+    "capf_session_csv_slow_floats": (c_int32, [_S, POINTER(c_int64)]),
     "capf_table_hash_route": (c_int32, [_T, c_int32, _STRS, c_int32, POINTER(c_int64), _PT]),
     "capf_table_download_device": (c_int32, [_T, c_char_p, c_void_p, c_void_p]),
     "capf_table_has_nulls": (c_int32, [_T, c_char_p, POINTER(c_int32)]),

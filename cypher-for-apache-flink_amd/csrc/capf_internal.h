@@ -426,6 +426,8 @@ struct Session {
   // set by capf_table_count_async for the duration of one call: the fused
   // count writes its result to this device int64 and does not wait
   int64_t *async_out = nullptr;
+  // FLOAT fields the last typed CSV parse converted on the host (capf_session_csv_slow_floats)
+  int64_t csv_slow_floats = 0;
 
   BufPtr alloc(size_t bytes);
   void sync();
@@ -607,6 +609,14 @@ void string_fn_codes(Session *s, int32_t fn, int64_t iarg0, int64_t iarg1, int64
 // split(subject, delimiter) per row of d (capf_table_str_split, string_fn.hip):
 // a LIST<STRING> column, its pieces interned on the device; both columns STRING.
 ColPtr str_split_column(Session *s, const Data &d, int subject_col, int delim_col);
+// Interning of the n results of a device step (string_fn.hip; index_mu held by
+// the caller, h = its heap snapshot of n0 strings): statuses st (ST_*), the
+// bytes rbytes[roff[i], roff[i + 1]) of a scratch heap of `total` bytes padded
+// by 16.  Returns the device codes (−1 NULL, −2 host, the source's code for an
+// identity); `out` non-null: copied to the host too.
+enum : uint8_t { ST_BYTES = 0, ST_IDENT = 1, ST_HOST = 2, ST_NULL = 3, ST_LONG = 4 };
+BufPtr intern_results(Session *s, const StringHeap &h, size_t n0, const int64_t *dsrc, int64_t c0, int64_t n,
+                      const BufPtr &st, const BufPtr &roff, const BufPtr &rbytes, int64_t total, int64_t *out);
 // Record an error for capf_last_error() (used by entry points outside runtime.cpp).
 int32_t record_error(int32_t code, const char *msg);
 

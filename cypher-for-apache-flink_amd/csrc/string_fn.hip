@@ -29,9 +29,10 @@
 // representative with an atomicMin of its position, and a prefix sum over the
 // representatives ranks them: new codes ascend in the order of the smallest
 // position producing each string, whatever the order the threads ran in.
-// The interning is one function (intern_results) with two callers: the string
-// functions above and split(subject, delimiter) per table row
-// (capf_table_str_split), whose kernels and byte formulas are at the end.
+// The interning is one function (intern_results) with three callers: the string
+// functions above, split(subject, delimiter) per table row
+// (capf_table_str_split), whose kernels and byte formulas are at the end, and
+// the STRING fields of the typed CSV parser (edge_list.hip).
 #include <algorithm>
 #include <cstring>
 
@@ -44,7 +45,7 @@ namespace capf {
 constexpr int SF_BLOCK = 256;
 constexpr int64_t SF_EMPTY = -1;
 constexpr int64_t SF_NEW = -3;  // out[i] between the probe and the assignment: not in the dictionary
-enum : uint8_t { ST_BYTES = 0, ST_IDENT = 1, ST_HOST = 2, ST_NULL = 3, ST_LONG = 4 };
+// (the result statuses ST_* are capf_internal.h's: intern_results is called from edge_list.hip too)
 
 struct FnArgs {
   int32_t fn;
@@ -525,7 +526,9 @@ static void ensure_index(Session *s, const StringHeap &h, size_t n) {
   if (n <= ix.n && ix.tab) return;
   const int64_t *off = (const int64_t *)h.off->p;
   const uint8_t *bytes = (const uint8_t *)h.bytes->p;
-  s->dict.reserve(ix.hashes, ix.hash_cap, n, 4096, 8, ix.n);  // the hashes so far move with it
+  // the hashes so far move with it; an empty dictionary (the typed CSV parser may be the first to
+  // intern anything) still gets a buffer: the probe takes its address
+  s->dict.reserve(ix.hashes, ix.hash_cap, std::max<size_t>(n, 1), 4096, 8, ix.n);
   const int64_t m = (int64_t)(n - ix.n);
   if (m > 0) {
     double by = 16.0 * (double)m;  // the strings' bytes, one offset and one hash per string
@@ -568,7 +571,7 @@ static int64_t read_counter(Session *s, const BufPtr &cnt) {
 // dictionary, their codes ascending by the smallest position producing each.
 // `out` non-null: the codes go to the host too, in the step's one
 // synchronisation; null: they stay on the device (split's element column).
-static BufPtr intern_results(Session *s, const StringHeap &h, size_t n0, const int64_t *dsrc, int64_t c0, int64_t n,
+BufPtr intern_results(Session *s, const StringHeap &h, size_t n0, const int64_t *dsrc, int64_t c0, int64_t n,
                              const BufPtr &st, const BufPtr &roff, const BufPtr &rbytes, int64_t total,
                              int64_t *out) {
   const int64_t *off = (const int64_t *)h.off->p;

@@ -14,11 +14,16 @@ Every table is read with the canonical field list of CAPFGraphExport
 relationships, then the properties sorted by their column name
 `property_<encoded key>`), no header, ',' between fields, '\\n' between rows
 — Flink's CsvTableSource defaults (FSGraphSource.scala:80-84).  A table
-whose declared fields are all LONG (node/rel ids and INTEGER properties: the
-shape of every R-MAT / LDBC edge table) is parsed on the GPU
-(capf_csv_read_longs, csrc/edge_list.hip); tables with STRING / FLOAT /
-BOOLEAN fields are parsed on the host and uploaded (strings are dictionary
-codes, interned host-side).  `graph(name)` returns the ScanGraph of element
+whose declared fields are all non-nullable LONG (node/rel ids and INTEGER
+properties: the shape of every R-MAT / LDBC edge table) is parsed on the GPU
+by capf_csv_read_longs (csrc/edge_list.hip); every other table — STRING,
+FLOAT, BOOLEAN, DATE, LOCALDATETIME or nullable fields — by the typed parser
+capf_csv_read_typed, its strings interned on the device.  The typed parser
+accepts a strict subset of what the host reader below (`_parse_csv`, the
+specification) accepts: a file it rejects is read again by the host reader,
+whose result or error is what the caller sees.  `routes` records which of the
+three ("longs", "typed", "host") produced each file.  The distributed session
+has neither device entry and keeps the host reader.  `graph(name)` returns the ScanGraph of element
 tables (AbstractPropertyGraphDataSource.graph, api/io/AbstractPropertyGraphDataSource.scala:87-108),
 `store(name, graph)` writes one (:126-160).
 
@@ -27,13 +32,18 @@ are pinned by the reference's own CSV graph (flink-cypher/src/main/resources/
 csv/products, committed as tests/golden/fs/products); how Flink's CSV source
 treats an empty field, a BOOLEAN spelling or a DOUBLE format is not covered
 by any reference fixture (parity unpinned): here an empty field is NULL,
-BOOLEAN is true/false (any case), DOUBLE is Python float syntax.
+BOOLEAN is true/false (any case), DOUBLE is Python float syntax.  The text of
+a DATE / LOCALDATETIME is unpinned too (the reference's Flink type mapping sends
+CTDate to LONG and no fixture holds a temporal): here ISO-8601, YYYY-MM-DD and
+YYYY-MM-DDTHH:MM:SS[.ffffff] (1 to 6 fraction digits read, `isoformat()` written).
 """
+import datetime
 import json
 import os
+import re
 import shutil
 
-from .expr import CT_TO_CAPF, T_BOOL, T_FLOAT, T_INT
+from .expr import CT_TO_CAPF, T_BOOL, T_DATE, T_FLOAT, T_INT, T_LOCALDATETIME
 
 SCHEMA_FILE = "propertyGraphSchema.json"
 META_FILE = "capsGraphMetaData.json"
@@ -101,6 +111,8 @@ class FSGraphSource:
         self.root = root
         self.table_storage_format = table_storage_format
         self._schema_cache = {}
+        # (file path, "longs" | "typed" | "host") per file read, in read order
+        self.routes = []
 
     # -- DefaultGraphDirectoryStructure ------------------------------------------
     def graph_dir(self, name):
@@ -192,19 +204,28 @@ class FSGraphSource:
     def _read_table(self, path, fields):
         names = [f for f, _ in fields]
         types = [CT_TO_CAPF[_base_type(ct)[0]] for _, ct in fields]
-        if any(_base_type(ct)[0] in ("DATE", "LOCALDATETIME") for _, ct in fields):
-            from ._lib import NotImplementedException
-            raise NotImplementedException(f"{path}: DATE / LOCALDATETIME fields in the CSV source")
         files = self._files(path)
         # The GPU LONG parser rejects an empty field; a nullable field ('INTEGER?')
-        # stores NULL as an empty field, so such tables take the host reader.
-        gpu = hasattr(self.session, "csv_read_longs") and not any(_base_type(ct)[1] for _, ct in fields)
+        # stores NULL as an empty field, so such tables take the typed parser.
+        longs = hasattr(self.session, "csv_read_longs") and all(t == T_INT for t in types) and \
+            not any(_base_type(ct)[1] for _, ct in fields)
+        typed = hasattr(self.session, "csv_read_typed")
         parts = []
         for fp in files:
-            if gpu and all(t == T_INT for t in types):
+            if longs:
                 parts.append(self.session.csv_read_longs(fp, ",", names))
-            else:
-                parts.append(self.session.table(_parse_csv(fp, types, names)))
+                self.routes.append((fp, "longs"))
+                continue
+            if typed:
+                from ._lib import IllegalArgumentException
+                try:
+                    parts.append(self.session.csv_read_typed(fp, ",", names, types))
+                    self.routes.append((fp, "typed"))
+                    continue
+                except IllegalArgumentException:
+                    pass  # outside the device grammars: the host reader decides
+            parts.append(self.session.table(_parse_csv(fp, types, names)))
+            self.routes.append((fp, "host"))
         if not parts:
             return self.session.empty(names, types)
         out = parts[0]
@@ -243,7 +264,7 @@ class FSGraphSource:
         data = [table.column_values(c) for c in cols]
         with open(os.path.join(path, "part-00000.csv"), "w", newline="") as f:
             for row in zip(*data):
-                f.write(",".join(_format_field(v) for v in row) + "\n")
+                f.write(",".join(_format_csv_field(v) for v in row) + "\n")
 
 
 def _schema_props(t):
@@ -270,6 +291,33 @@ def _format_field(v):
     return str(v)
 
 
+def _format_csv_field(v):
+    """The field text `store` writes.  Temporals are handled here and not in
+    _format_field, whose refusal of them is pinned by an existing test
+    (tests/test_temporal.py::test_csv_source_refuses_temporal_values); every
+    other value is _format_field's."""
+    if isinstance(v, (datetime.date, datetime.datetime)):
+        return v.isoformat()  # YYYY-MM-DD | YYYY-MM-DDTHH:MM:SS[.ffffff]
+    return _format_field(v)
+
+
+# The two temporal grammars, written out (datetime.fromisoformat accepts more,
+# and more again on newer Pythons); the device parser has the same two.
+_DATE_RE = re.compile(r"([0-9]{4})-([0-9]{2})-([0-9]{2})")
+_DATETIME_RE = re.compile(r"([0-9]{4})-([0-9]{2})-([0-9]{2})T([0-9]{2}):([0-9]{2}):([0-9]{2})(?:\.([0-9]{1,6}))?")
+
+
+def _parse_temporal(s, t):
+    m = (_DATE_RE if t == T_DATE else _DATETIME_RE).fullmatch(s)
+    if m is None:
+        raise ValueError(s)
+    y, mo, d = int(m.group(1)), int(m.group(2)), int(m.group(3))
+    if t == T_DATE:
+        return datetime.date(y, mo, d)  # ValueError outside 0001-9999 / the month's days
+    frac = (m.group(7) or "").ljust(6, "0")
+    return datetime.datetime(y, mo, d, int(m.group(4)), int(m.group(5)), int(m.group(6)), int(frac))
+
+
 def _parse_field(s, t, line, path):
     if s == "":
         return None
@@ -285,6 +333,8 @@ def _parse_field(s, t, line, path):
             if low not in ("true", "false"):
                 raise ValueError(s)
             return low == "true"
+        if t in (T_DATE, T_LOCALDATETIME):
+            return _parse_temporal(s, t)
     except ValueError:
         raise ValueError(f"{path}: line {line} could not be parsed: {s!r} is not a {t}") from None
     return s

@@ -291,6 +291,32 @@ class GpuSession:
                   _lib.strs(list(names)), byref(h))
         return GpuTable(self, h)
 
+    def csv_read_typed(self, path, sep, names, types):
+        """A CSV table with typed fields (T_INT, T_FLOAT, T_BOOL, T_STRING,
+        T_DATE, T_LOCALDATETIME; an empty field is NULL), parsed on the GPU
+        (capf_csv_read_typed).  IllegalArgumentException names the first line
+        outside the grammars of include/capf_gpu.h."""
+        h = c_void_p()
+        k = len(names)
+        _lib.call("capf_csv_read_typed", self._h, os.fsencode(path), sep.encode(), k, _lib.strs(list(names)),
+                  (c_int32 * max(k, 1))(*types), byref(h))
+        return GpuTable(self, h)
+
+    def csv_parse_typed(self, data, sep, names, types):
+        h = c_void_p()
+        buf = bytes(data)
+        k = len(names)
+        _lib.call("capf_csv_parse_typed", self._h, buf, len(buf), sep.encode(), k, _lib.strs(list(names)),
+                  (c_int32 * max(k, 1))(*types), byref(h))
+        return GpuTable(self, h)
+
+    def csv_slow_floats(self):
+        """FLOAT fields that the last csv_*_typed call converted on the host
+        (outside the device's exact path: mantissa > 2^53 or |power of ten| > 22)."""
+        v = c_int64()
+        _lib.call("capf_session_csv_slow_floats", self._h, byref(v))
+        return v.value
+
     def var_length_reach(self, rels, src_col, dst_col, sources, source_id_col, targets, target_id_col,
                          lower, upper, out_source_col, out_reach_col):
         """Fused VarLengthExpand → Distinct(a, b) → Aggregate(a, count(*))

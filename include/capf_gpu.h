@@ -687,6 +687,37 @@ capf_status capf_csv_parse_longs(capf_session *s, const char *bytes, int64_t nby
 capf_status capf_csv_read_longs(capf_session *s, const char *path, const char *sep,
                                 int32_t ncols, const char *const *names, capf_table **out);
 
+/* CSV tables of an FS graph source with typed fields, parsed on the GPU: one
+ * column per declared field, in file order, of type types[i] — CAPF_TYPE_INT64,
+ * FLOAT64, BOOL, STRING, DATE or LOCALDATETIME (anything else is
+ * IllegalArgument).  ncols ≤ 16; sep is 1 to 8 ASCII bytes; text after the last
+ * declared field is not parsed.  Lines as Python's text mode reads them: '\n'
+ * ends a line, one '\r' directly before it (or at the end of the file) is
+ * stripped, any other '\r' rejects the file, as does a line with fewer fields
+ * than declared.  An empty field is NULL for every type; a column without a
+ * NULL carries no validity mask.  Fields:
+ *   INT64          optional '-' and ASCII digits within int64 (as _longs)
+ *   BOOL           true | false, ASCII case-insensitive
+ *   DATE           YYYY-MM-DD, year 0001-9999, a day of the Gregorian month
+ *   LOCALDATETIME  YYYY-MM-DDTHH:MM:SS[.f{1,6}], hour ≤ 23, minute, second ≤ 59
+ *   FLOAT64        [+-]?(\d+(\.\d*)?|\.\d+)([eE][+-]?\d+)?, correctly rounded
+ *                  (the device converts mantissas ≤ 2^53 with |power of ten|
+ *                  ≤ 22 exactly; the others are converted on the host after the
+ *                  kernel — capf_session_csv_slow_floats counts them)
+ *   STRING         the field's bytes, interned on the device: strict UTF-8
+ *                  without 0x00
+ * A byte ≥ 0x80 outside a STRING field (the unparsed text included) rejects
+ * the file.  A rejection is IllegalArgument, "CSV line N could not be parsed:
+ * <reason>", N the first bad line (1-based).  No quoting, no comment prefix. */
+capf_status capf_csv_parse_typed(capf_session *s, const char *bytes, int64_t nbytes, const char *sep,
+                                 int32_t ncols, const char *const *names, const int32_t *types,
+                                 capf_table **out);
+capf_status capf_csv_read_typed(capf_session *s, const char *path, const char *sep,
+                                int32_t ncols, const char *const *names, const int32_t *types,
+                                capf_table **out);
+/* FLOAT64 fields that the session's last capf_csv_*_typed call converted on the host. */
+capf_status capf_session_csv_slow_floats(capf_session *s, int64_t *out);
+
 /* ------------------------------------------------- distributed Table layer
  * The exchange of a hash-partitioned Table over G ranks (dist_table.py):
  * Flink's join and groupBy repartition both inputs by a hash of the key

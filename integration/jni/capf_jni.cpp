@@ -771,6 +771,33 @@ JNI(jlong, csvParseLongs)(JNIEnv *env, jobject, jlong s, jobject bytes, jlong nb
              ? 0
              : H(out);
 }
+// FS graph source: CSV tables with typed fields (types.length = names.length; an
+// array that is shorter fails as IllegalArgument before the native call)
+JNI(jlong, csvReadTyped)(JNIEnv *env, jobject, jlong s, jstring path, jstring sep, jobjectArray names,
+                         jintArray types) {
+  JStr p(env, path), d(env, sep);
+  JStrs nm(env, names);
+  const std::vector<int32_t> ty = ints(env, types);
+  capf_table *out = nullptr;
+  const int32_t k = (int)ty.size() == nm.n() ? nm.n() : -1;
+  return fail(env, capf_csv_read_typed(S(s), p.p, d.p, k, nm.data(), ty.data(), &out)) ? 0 : H(out);
+}
+JNI(jlong, csvParseTyped)(JNIEnv *env, jobject, jlong s, jobject bytes, jlong nbytes, jstring sep,
+                          jobjectArray names, jintArray types) {
+  JStr d(env, sep);
+  JStrs nm(env, names);
+  const std::vector<int32_t> ty = ints(env, types);
+  capf_table *out = nullptr;
+  const int32_t k = (int)ty.size() == nm.n() ? nm.n() : -1;
+  return fail(env, capf_csv_parse_typed(S(s), (const char *)direct(env, bytes), nbytes, d.p, k, nm.data(),
+                                        ty.data(), &out))
+             ? 0
+             : H(out);
+}
+JNI(jlong, sessionCsvSlowFloats)(JNIEnv *env, jobject, jlong s) {
+  int64_t n = 0;
+  return fail(env, capf_session_csv_slow_floats(S(s), &n)) ? 0 : (jlong)n;
+}
 // distributed Table layer: hash routing + device-side column copies; the
 // JVM side moves the [off[p], off[p+1]) slices with its collective library
 // (counts → countsOut[0..parts))

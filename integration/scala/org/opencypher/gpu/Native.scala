@@ -263,6 +263,13 @@ object Native {
   @native def csvReadLongs(session: Long, path: String, sep: String, names: Array[String]): Long
   @native def csvParseLongs(session: Long, bytes: java.nio.ByteBuffer, nBytes: Long, sep: String,
                             names: Array[String]): Long
+  // FS graph source: CSV tables with typed fields (Type* constants; an empty field is NULL) parsed on the
+  // GPU; IllegalArgument names the first line outside the grammars of capf_gpu.h
+  @native def csvReadTyped(session: Long, path: String, sep: String, names: Array[String], types: Array[Int]): Long
+  @native def csvParseTyped(session: Long, bytes: java.nio.ByteBuffer, nBytes: Long, sep: String,
+                            names: Array[String], types: Array[Int]): Long
+  // FLOAT fields the session's last csv*Typed call converted on the host
+  @native def sessionCsvSlowFloats(session: Long): Long
   // distributed Table layer (dist_table.py): rows grouped by owner h(keys), counts per owner
   @native def tableHashRoute(table: Long, keys: Array[String], parts: Int, countsOut: Array[Long]): Long
   @native def tableDownloadDevice(table: Long, col: String, dValues: Long, dValid: Long): Unit
