@@ -175,6 +175,16 @@ _SIGS = {
     "capf_table_from_packed_rows": (c_int32, [_S, c_int32, POINTER(c_char_p), POINTER(c_int32), POINTER(c_int32),
                                               POINTER(c_int64), POINTER(c_int32), c_void_p, c_int64,
                                               POINTER(_T)]),
+    "capf_table_list_stats": (c_int32, [_T, c_char_p, POINTER(c_int32), POINTER(c_int64), POINTER(c_int64),
+                                        POINTER(c_int32), POINTER(c_int32), POINTER(c_int64), POINTER(c_int64),
+                                        POINTER(c_int64)]),
+    "capf_table_pack_list_elems": (c_int32, [_T, c_char_p, c_int32, POINTER(c_int64), c_int32, c_int32, c_int64,
+                                             c_int32, POINTER(c_int64), POINTER(c_int32), c_void_p]),
+    "capf_table_from_packed_lists": (c_int32, [_S, c_int32, POINTER(c_char_p), POINTER(c_int32), POINTER(c_int32),
+                                               POINTER(c_int64), POINTER(c_int32), c_void_p, c_int64, c_int32,
+                                               POINTER(c_int32), POINTER(c_int32), POINTER(c_int64),
+                                               POINTER(c_int32), POINTER(c_void_p), POINTER(c_int64),
+                                               POINTER(_T)]),
     "capf_dot_u32": (c_int32, [_S, c_void_p, c_void_p, c_int64, POINTER(c_uint64)]),
     "capf_comm_unique_id": (c_int32, [c_void_p]),
     "capf_comm_init": (c_int32, [_S, c_int32, c_int32, c_void_p, _PT]),

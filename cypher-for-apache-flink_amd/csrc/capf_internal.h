@@ -672,6 +672,20 @@ void pack_rows(Session *s, const std::vector<ColPtr> &cols, const int32_t *width
                const int32_t *nullable, int64_t n, int *W, void *d_out);
 ColPtr unpack_column(Session *s, const void *rows, int64_t n, int W, int off, int width, int voff, int64_t base,
                      Type t);
+// LIST columns on the wire (shuffle.hip): a length field in the row, the
+// elements as a stream of records beside it.  list_offsets_at: the offsets at
+// rows `pos` (host);  list_max_len: the longest non-NULL list;  pack_list_elems:
+// child rows [first, first + total) as records of `width` bytes of (value − base)
+// (+ a validity byte);  unpack_list_column: the column of n packed rows and
+// their n_elems records (IllegalArgument when the lengths do not sum to n_elems).
+// c itself, or (when a NULL list of c owns elements) a copy without them: on the wire a NULL list is empty
+ColPtr list_without_null_extents(Session *s, const ColPtr &c);
+std::vector<int64_t> list_offsets_at(Session *s, const ColPtr &c, const std::vector<int64_t> &pos);
+int64_t list_max_len(Session *s, const ColPtr &c);
+void pack_list_elems(Session *s, const ColPtr &child, int64_t first, int64_t total, int width, int64_t base,
+                     bool with_valid, void *d_out);
+ColPtr unpack_list_column(Session *s, const void *rows, int64_t n, int W, int off, int width, int voff,
+                          const void *d_elems, int64_t n_elems, int ewidth, int64_t ebase, bool evalid, Type et);
 // Rows of `keys` (n rows) grouped by owner h(key tuple) of `parts` (shuffle.hip):
 // the permutation (int64 row indexes) and the row count per owner.
 BufPtr route_permutation(Session *s, const std::vector<ColView> &keys, int64_t n, int parts,

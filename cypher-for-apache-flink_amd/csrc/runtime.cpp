@@ -1402,8 +1402,6 @@ capf_status capf_table_hash_route(capf_table *t, int32_t nkeys, const char *cons
     force(kc);
     kv.push_back(view_of(kc));
   }
-  for (const ColPtr &c : d->cols)
-    if (c->type == Type::List) illegal("LIST columns are not routed between ranks");
   std::vector<int64_t> cnt;
   BufPtr perm = route_permutation(s, kv, d->nrows, parts, cnt);
   auto n = new_node(s, Kind::Source);
@@ -1468,8 +1466,10 @@ capf_status capf_table_column_range(capf_table *t, const char *col, int64_t *mn,
   CAPF_API_END
 }
 
-static void check_wire(Type t, int32_t width, int64_t base) {
-  const bool ok = t == Type::Null     ? width == 0
+// lists: a LIST column's length field (4 or 8 bytes) is allowed
+static void check_wire(Type t, int32_t width, int64_t base, bool lists = false) {
+  const bool ok = t == Type::List     ? lists && (width == 4 || width == 8) && base == 0
+                  : t == Type::Null   ? width == 0
                   : t == Type::Bool   ? width == 1
                   : t == Type::Float64 ? width == 8 && base == 0
                   : (is_int_payload(t) || t == Type::String) ? (width == 3 || width == 4 || (width == 8 && base == 0))
@@ -1496,7 +1496,7 @@ capf_status capf_table_pack_rows(capf_table *t, int32_t ncols, const char *const
   for (int j = 0; j < ncols; ++j) {
     need(cols[j], "col");
     const int i = t->node->col_index_or_throw(cols[j]);
-    check_wire(t->node->types[i], width[j], base[j]);
+    check_wire(t->node->types[i], width[j], base[j], true);
     force(d->cols[i]);
     if (!nullable[j] && d->cols[i]->valid && d->cols[i]->type != Type::Null)
       illegal("packed rows: a column with NULLs needs its validity byte");
@@ -1544,6 +1544,176 @@ capf_status capf_table_from_packed_rows(capf_session *cs, int32_t ncols, const c
     n->names.push_back(nm[j]);
     n->types.push_back((Type)types[j]);
     e->cols.push_back(unpack_column(s, d_rows, nrows, W, off[j], width[j], voff[j], base[j], (Type)types[j]));
+  }
+  s->sync();
+  n->result = e;
+  *out = wrap(n);
+  CAPF_API_END
+}
+
+// ---- LIST columns on the wire (shuffle.hip "list elements")
+static const ColPtr &list_col_or_throw(capf_table *t, const DataPtr &d, const char *col) {
+  const int i = t->node->col_index_or_throw(col);
+  if (t->node->types[i] != Type::List) illegal("column '" + std::string(col) + "' is not a LIST");
+  force(d->cols[i]);
+  return d->cols[i];
+}
+
+static void check_elem_type(int32_t et) {
+  if (et < CAPF_TYPE_NULL || et > CAPF_TYPE_STRING) illegal("bad list element type");
+}
+
+capf_status capf_table_list_stats(capf_table *t, const char *col, int32_t *elem_type, int64_t *longest,
+                                  int64_t *n_elems, int32_t *elem_nulls, int32_t *elem_enc, int64_t *mn,
+                                  int64_t *mx, int64_t *non_null) {
+  CAPF_API_BEGIN
+  need(t, "table");
+  need(col, "col");
+  need(elem_type, "elem_type");
+  need(longest, "longest");
+  need(n_elems, "n_elems");
+  need(elem_nulls, "elem_nulls");
+  need(elem_enc, "elem_enc");
+  need(mn, "min");
+  need(mx, "max");
+  need(non_null, "non_null");
+  DataPtr d = materialize(t->node);
+  Session *s = t->node->s;
+  const ColPtr c = list_without_null_extents(s, list_col_or_throw(t, d, col));
+  const ColPtr &ch = c->child;
+  const std::vector<int64_t> o = list_offsets_at(s, c, {0, c->n});
+  *elem_type = (int32_t)ch->type;
+  *n_elems = o[1] - o[0];
+  *longest = list_max_len(s, c);
+  *elem_nulls = ch->type == Type::Null ? (*n_elems > 0) : (ch->valid != nullptr);
+  *elem_enc = ch->enc;
+  *mn = 0;
+  *mx = -1;
+  *non_null = 0;
+  if ((ch->type == Type::Int64 || ch->type == Type::String) && ch->n > 0) {
+    // (over the whole child: a superset of the listed elements only widens the range)
+    const ColStats &st = column_stats(s, ch);
+    *mn = st.min;
+    *mx = st.max;
+    *non_null = st.non_null;
+  }
+  CAPF_API_END
+}
+
+capf_status capf_table_pack_list_elems(capf_table *t, const char *col, int32_t nparts, const int64_t *row_counts,
+                                       int32_t elem_type, int32_t width, int64_t base, int32_t elem_nullable,
+                                       int64_t *elem_counts, int32_t *rec_bytes, void *d_out) {
+  CAPF_API_BEGIN
+  need(t, "table");
+  need(col, "col");
+  need(row_counts, "row_counts");
+  need(elem_counts, "elem_counts");
+  need(rec_bytes, "rec_bytes");
+  if (nparts <= 0 || nparts > (1 << 20)) illegal("parts out of range");
+  check_elem_type(elem_type);
+  check_wire((Type)elem_type, width, base);
+  if (elem_type == CAPF_TYPE_NULL && elem_nullable) illegal("packed elements: NULL-typed elements carry no validity byte");
+  DataPtr d = materialize(t->node);
+  Session *s = t->node->s;
+  // (elements of NULL lists, where any are stored, stay behind: the row's length field is 0)
+  const ColPtr c = list_without_null_extents(s, list_col_or_throw(t, d, col));
+  const ColPtr &ch = c->child;
+  std::vector<int64_t> pos(nparts + 1, 0);
+  for (int p = 0; p < nparts; ++p) {
+    if (row_counts[p] < 0 || row_counts[p] > d->nrows - pos[p]) illegal("packed elements: row counts do not sum to the table's rows");
+    pos[p + 1] = pos[p] + row_counts[p];
+  }
+  if (pos[nparts] != d->nrows) illegal("packed elements: row counts do not sum to the table's rows");
+  if (ch->type != Type::Null && (int32_t)ch->type != elem_type)
+    illegal(std::string("packed elements: the column holds LIST<") + type_name(ch->type) + ">, not LIST<" +
+            type_name((Type)elem_type) + ">");
+  const std::vector<int64_t> o = list_offsets_at(s, c, pos);
+  const int64_t first = o[0], total = o[nparts] - o[0];
+  for (int p = 0; p < nparts; ++p) {
+    if (o[p + 1] < o[p]) fail(CAPF_ERR_INTERNAL, "list offsets decrease");
+    elem_counts[p] = o[p + 1] - o[p];
+  }
+  if (first < 0 || first + total > ch->n) fail(CAPF_ERR_INTERNAL, "list offsets outside the element column");
+  const bool child_nulls = ch->type == Type::Null ? (elem_type != CAPF_TYPE_NULL && total > 0) : ch->valid != nullptr;
+  if (child_nulls && !elem_nullable) illegal("packed elements: a list with NULL elements needs its validity byte");
+  const int rec = width + (elem_nullable ? 1 : 0);
+  *rec_bytes = rec;
+  if (d_out && total > 0 && rec > 0) {
+    if ((uintptr_t)d_out % (rec == 8 ? 8 : 4))
+      illegal("packed elements: the output buffer must be 4-byte aligned (8-byte for 8-byte records)");
+    pack_list_elems(s, ch, first, total, width, base, elem_nullable != 0, d_out);
+    s->sync();
+  }
+  CAPF_API_END
+}
+
+capf_status capf_table_from_packed_lists(capf_session *cs, int32_t ncols, const char *const *names,
+                                         const int32_t *types, const int32_t *width, const int64_t *base,
+                                         const int32_t *nullable, const void *d_rows, int64_t nrows, int32_t nlists,
+                                         const int32_t *elem_types, const int32_t *elem_width,
+                                         const int64_t *elem_base, const int32_t *elem_nullable,
+                                         const void *const *d_elems, const int64_t *n_elems, capf_table **out) {
+  CAPF_API_BEGIN
+  need(cs, "session");
+  need(out, "out");
+  if (ncols < 0 || nrows < 0 || nlists < 0) illegal("negative size");
+  if (ncols > 0) {
+    need(names, "names");
+    need(types, "types");
+    need(width, "width");
+    need(base, "base");
+    need(nullable, "nullable");
+  }
+  if (nlists > 0) {
+    need(elem_types, "elem_types");
+    need(elem_width, "elem_width");
+    need(elem_base, "elem_base");
+    need(elem_nullable, "elem_nullable");
+    need(d_elems, "elems");
+    need(n_elems, "n_elems");
+  }
+  Session *s = &cs->impl;
+  int W = 0, nl = 0;
+  std::vector<int> off(ncols), voff(ncols);
+  std::vector<std::string> nm;
+  for (int j = 0; j < ncols; ++j) {
+    need(names[j], "name");
+    nm.emplace_back(names[j]);
+    check_wire((Type)types[j], width[j], base[j], true);
+    nl += types[j] == CAPF_TYPE_LIST;
+    off[j] = W;
+    W += width[j];
+    voff[j] = nullable[j] ? W++ : -1;
+  }
+  if (nl != nlists) illegal("packed lists: one element stream per LIST column");
+  for (int l = 0; l < nlists; ++l) {
+    check_elem_type(elem_types[l]);
+    check_wire((Type)elem_types[l], elem_width[l], elem_base[l]);
+    if (elem_types[l] == CAPF_TYPE_NULL && elem_nullable[l])
+      illegal("packed elements: NULL-typed elements carry no validity byte");
+    if (n_elems[l] < 0) illegal("negative size");
+    const int rec = elem_width[l] + (elem_nullable[l] ? 1 : 0);
+    if (n_elems[l] > 0 && rec > 0) {
+      need(d_elems[l], "elems");
+      if ((uintptr_t)d_elems[l] % 4) illegal("packed elements: the stream must be 4-byte aligned");
+    }
+  }
+  check_unique_names(nm);
+  if (nrows > 0 && W > 0) need(d_rows, "rows");
+  auto n = new_node(s, Kind::Source);
+  auto e = std::make_shared<Data>();
+  e->nrows = nrows;
+  int l = 0;
+  for (int j = 0; j < ncols; ++j) {
+    n->names.push_back(nm[j]);
+    n->types.push_back((Type)types[j]);
+    if (types[j] == CAPF_TYPE_LIST) {
+      e->cols.push_back(unpack_list_column(s, d_rows, nrows, W, off[j], width[j], voff[j], d_elems[l], n_elems[l],
+                                           elem_width[l], elem_base[l], elem_nullable[l] != 0, (Type)elem_types[l]));
+      ++l;
+    } else {
+      e->cols.push_back(unpack_column(s, d_rows, nrows, W, off[j], width[j], voff[j], base[j], (Type)types[j]));
+    }
   }
   s->sync();
   n->result = e;
@@ -1822,9 +1992,13 @@ capf_status capf_table_download_list(capf_table *t, const char *col, int64_t *of
   s->sync();
   if (offsets_out)
     HIP_CHECK(hipMemcpyAsync(offsets_out, c->data->p, 8 * (n + 1), hipMemcpyDeviceToHost, s->stream));
-  if (values_out && total > 0 && c->child->type != Type::Null)
-    HIP_CHECK(hipMemcpyAsync(values_out, c->child->data->p, type_width(c->child->type) * total,
-                             hipMemcpyDeviceToHost, s->stream));
+  if (values_out && total > 0 && c->child->type != Type::Null) {
+    // (a list that came over the exchange keeps a FOR24 / FOR32 element column)
+    const ColPtr ch = decode_column(s, c->child);
+    HIP_CHECK(hipMemcpyAsync(values_out, ch->data->p, type_width(ch->type) * total, hipMemcpyDeviceToHost,
+                             s->stream));
+    s->sync();  // ch may be a temporary
+  }
   if (valid_out && n > 0) {
     if (c->valid)
       HIP_CHECK(hipMemcpyAsync(valid_out, c->valid->p, n, hipMemcpyDeviceToHost, s->stream));

@@ -43,6 +43,16 @@ GPU (capf_table_hash_route, csrc/shuffle.hip) and moves them with ONE
 all_to_all_single per shuffle (RCCL over xGMI; host-staged under gloo), the
 columns packed row-major; the CPU tests drive the same DistTable logic over
 the numpy oracle with their own exchange.
+
+All eight column types move.  DATE and LOCALDATETIME columns travel like
+INTEGER columns (range, FOR24 / FOR32 / 8 bytes) and keep their type.  A LIST
+column puts a 4- or 8-byte length field into its row; its elements follow as
+the packed rows of the child column (include/capf_gpu.h "LIST columns"), which
+costs a table with LIST columns one more counts all-to-all (the element counts
+of all its LIST columns together) and one element all-to-all per LIST column.
+A table without LIST columns issues the two collectives it always did.  A
+LIST column is never a routing key: the other keys route (a subset of a key
+tuple routes correctly), and rows keyed by lists alone are gathered to rank 0.
 """
 from ctypes import byref, c_int32, c_int64, c_uint64, c_void_p
 
@@ -55,6 +65,53 @@ from .expr import (AGG_AVG, AGG_COUNT, AGG_COUNT_STAR, AGG_MAX, AGG_MIN, AGG_SUM
 from .header import RecordHeader
 
 ROUTE_MAXK = 8  # routing keys per shuffle (shuffle.hip); a subset of a key tuple routes correctly
+T_LIST, T_DATE, T_LOCALDATETIME = 5, 6, 7  # CAPF_TYPE_LIST / _DATE / _LOCALDATETIME
+_INT_PAYLOAD = (T_INT, T_STRING, T_DATE, T_LOCALDATETIME)  # int64 values on the wire: ranged, FOR24 / FOR32 / 8
+_BIG = (1 << 63) - 1
+LIST_ENTRIES = 6  # per LIST column in the layout all-reduce: type, longest, NULL flag, −min, max, −type
+
+
+def value_width(gmin, gmax):
+    """(width, base) of an integer payload whose values over all ranks span
+    [gmin, gmax] (gmax < gmin: no value anywhere): (value − base) in 3 bytes
+    below a range of 2^24, 4 below 2^32, else the plain 8 bytes."""
+    if gmax < gmin:
+        return 3, 0
+    if gmax - gmin < (1 << 24):
+        return 3, gmin
+    if gmax - gmin < (1 << 32):
+        return 4, gmin
+    return 8, 0
+
+
+def range_entries(mn, mx, non_null):
+    """One rank's (−min, max) entries of the layout's MAX all-reduce for an
+    integer payload with values in [mn, mx] (non_null of them).  No value:
+    both −_BIG, the lowest.  −INT64_MIN does not fit an int64, so a minimum of
+    INT64_MIN sends (_BIG, _BIG): the agreed range is then wider than 2^32 on
+    every rank and the values travel in the plain 8 bytes."""
+    if not non_null:
+        return -_BIG, -_BIG
+    if mn == -(1 << 63):
+        return _BIG, _BIG
+    return -mn, mx
+
+
+def length_width(longest):
+    """Bytes of a LIST column's length field: 4 while the longest list over
+    all ranks has fewer than 2^31 elements, else 8."""
+    return 4 if longest < (1 << 31) else 8
+
+
+def scalar_wire(t, gmin, gmax):
+    """(width, base) of one value of type t (a column's, or a list's elements)."""
+    if t == T_NULL:
+        return 0, 0
+    if t == T_BOOL:
+        return 1, 0
+    if t in _INT_PAYLOAD:
+        return value_width(gmin, gmax)
+    return 8, 0
 
 
 class GpuExchange:
@@ -88,7 +145,7 @@ class GpuExchange:
     # -- row movement -----------------------------------------------------------
     def route(self, table, keys):
         """(table with rows grouped by owner, per-owner row counts)."""
-        keys = list(keys)[:ROUTE_MAXK]
+        keys = [k for k in keys if table.capf_type(k) != T_LIST][:ROUTE_MAXK]
         counts = (c_int64 * self.world)()
         h = c_void_p()
         _lib.call("capf_table_hash_route", table._h, len(keys), _lib.strs(keys), self.world, counts, byref(h))
@@ -96,12 +153,18 @@ class GpuExchange:
         return GpuTable(self.s, h), list(counts)
 
     def shuffle(self, table, keys):
+        if all(table.capf_type(k) == T_LIST for k in keys):
+            # no routable key: the rows meet on rank 0 (equal keys on one rank)
+            return self.to_root(table)
         routed, counts = self.route(table, keys)
         return self.send(routed, counts)
 
     def own_share(self, table, keys):
         """Rows of a table every rank holds in full that this rank owns by
-        h(keys) (sharding at ingest: no exchange)."""
+        h(keys) (sharding at ingest: no exchange).  Keys that are all LIST
+        columns route nothing: rank 0 keeps every row."""
+        if all(table.capf_type(k) == T_LIST for k in keys):
+            return table if self.rank == 0 else table.limit(0)
         routed, counts = self.route(table, keys)
         off = sum(counts[:self.rank])
         return routed.skip(off).limit(counts[self.rank]).cache()
@@ -123,68 +186,100 @@ class GpuExchange:
         width of (value − base) — FOR24 / FOR32 where the value range over ALL
         ranks fits 24 / 32 bits, 8 B otherwise — and whether it carries a
         validity byte.  Everything is agreed in ONE int64 MAX all-reduce: the
-        local NULL flags, −min and max of every INTEGER / STRING column, and
-        (STRING columns travel as dictionary codes) the dictionary size and
-        digest with their negations (min == max on every rank)."""
+        local NULL flags, −min and max of every INTEGER / STRING / DATE /
+        LOCALDATETIME column, (STRING values travel as dictionary codes) the
+        dictionary size and digest with their negations (min == max on every
+        rank), and per LIST column the element type (NULL = 0 is the lowest: a
+        rank whose shard is empty or NULL-typed adopts the others' type), the
+        longest list, the element NULL flag, −min / max of INTEGER / STRING
+        elements and −type (the ranks' non-NULL element types must be equal:
+        checked on every rank before any further collective).  The vector's length depends on the column types alone (the
+        dictionary entries go with any STRING or LIST column), so every rank
+        reduces the same vector; the dictionaries must agree only when STRING
+        values move, in a column or as the elements of a list.
+        → (cols, types, width, base, nullable, lists); lists: per LIST column
+        (column, element type, element width, element base, element nullable)."""
         cols = table.physicalColumns
         types = [table.capf_type(c) for c in cols]
-        if any(t not in (0, 1, 2, 3, 4) for t in types):
-            raise _lib.NotImplementedException("LIST, DATE and LOCALDATETIME columns are not moved between ranks")
         k = len(cols)
         has, lo, hi = [], [], []
-        big = (1 << 63) - 1
+        lcols = [c for c, t in zip(cols, types) if t == T_LIST]
+        lstats = []
         for c, t in zip(cols, types):
             v = c_int32()
             _lib.call("capf_table_has_nulls", table._h, c.encode(), byref(v))
             has.append(v.value)
-            if t in (T_INT, T_STRING):
+            if t in _INT_PAYLOAD:
                 mn, mx, nn = c_int64(), c_int64(), c_int64()
                 _lib.call("capf_table_column_range", table._h, c.encode(), byref(mn), byref(mx), byref(nn))
-                lo.append(-mn.value if nn.value else -big)
-                hi.append(mx.value if nn.value else -big)
+                a, b = range_entries(mn.value, mx.value, nn.value)
+                lo.append(a), hi.append(b)
             else:
-                lo.append(-big)
-                hi.append(-big)
+                lo.append(-_BIG)
+                hi.append(-_BIG)
+            if t == T_LIST:
+                et, en, enc = c_int32(), c_int32(), c_int32()
+                longest, ne, mn, mx, nn = c_int64(), c_int64(), c_int64(), c_int64(), c_int64()
+                _lib.call("capf_table_list_stats", table._h, c.encode(), byref(et), byref(longest), byref(ne),
+                          byref(en), byref(enc), byref(mn), byref(mx), byref(nn))
+                lstats += [et.value, longest.value, en.value, *range_entries(mn.value, mx.value, nn.value),
+                           -et.value if et.value != T_NULL else -_BIG]
         check = []
-        if T_STRING in types:
+        if T_STRING in types or lcols:
             cnt, dig = c_int64(), c_uint64()
             _lib.call("capf_string_digest", self.s._h, byref(cnt), byref(dig))
             d = dig.value - (1 << 64) if dig.value >= (1 << 63) else dig.value
-            check = [cnt.value, -cnt.value, d, -d if d != -(1 << 63) else big]
-        got = self.all_max_i64(has + lo + hi + check)
-        if check:
+            check = [cnt.value, -cnt.value, d, -d if d != -(1 << 63) else _BIG]
+        got = self.all_max_i64(has + lo + hi + check + lstats)
+        l0 = 3 * k + len(check)
+        etypes = [got[l0 + LIST_ENTRIES * i] for i in range(len(lcols))]
+        for i, c in enumerate(lcols):
+            # max and min of the ranks' non-NULL element types must agree: raised on every
+            # rank, before any rank enters the exchange's collectives
+            low = got[l0 + LIST_ENTRIES * i + 5]
+            if low != -_BIG and -low != etypes[i]:
+                raise _lib.IllegalStateException(
+                    f"LIST column '{c}' holds elements of different types on different ranks "
+                    f"(types {-low} and {etypes[i]}): it cannot be exchanged")
+        if check and (T_STRING in types or T_STRING in etypes):
             c0 = 3 * k
             if got[c0] != -got[c0 + 1] or (got[c0 + 2] != -got[c0 + 3] and check[2] != -(1 << 63)):
                 raise _lib.IllegalStateException(
                     "string dictionaries differ between ranks: STRING columns cannot be exchanged as codes")
         # an all-NULL column is rebuilt from its type alone
         nullable = [bool(x) and t != T_NULL for x, t in zip(got[:k], types)]
-        width, base = [], []
+        width, base, lists = [], [], []
         for j, t in enumerate(types):
-            if t == T_NULL:
-                width.append(0), base.append(0)
-            elif t == T_BOOL:
-                width.append(1), base.append(0)
-            elif t in (T_INT, T_STRING):
-                gmin, gmax = -got[k + j], got[2 * k + j]
-                if gmax < gmin:  # no value anywhere
-                    width.append(3), base.append(0)
-                elif gmax - gmin < (1 << 24):
-                    width.append(3), base.append(gmin)
-                elif gmax - gmin < (1 << 32):
-                    width.append(4), base.append(gmin)
-                else:
-                    width.append(8), base.append(0)
+            if t == T_LIST:
+                g = got[l0 + LIST_ENTRIES * len(lists):l0 + LIST_ENTRIES * len(lists) + 5]
+                ew, eb = scalar_wire(g[0], -g[3], g[4])
+                lists.append((cols[j], g[0], ew, eb, bool(g[2]) and g[0] != T_NULL))
+                width.append(length_width(g[1])), base.append(0)
             else:
-                width.append(8), base.append(0)
-        return cols, types, width, base, nullable
+                w, b = scalar_wire(t, -got[k + j], got[2 * k + j])
+                width.append(w), base.append(b)
+        return cols, types, width, base, nullable, lists
+
+    def _all_to_all_rows(self, rows, send_counts, recv_counts, dev):
+        """rows[(Σ send_counts, W) bytes on the GPU] → the (Σ recv_counts, W)
+        bytes received (on the GPU; host-staged under gloo)."""
+        m, W = sum(recv_counts), rows.shape[1]
+        out = torch.empty((max(m, 1), W), dtype=torch.uint8, device=dev)[:m]
+        if W > 0:
+            src = rows.to(dev) if self.staged else rows
+            dist.all_to_all_single(out, src, list(recv_counts), list(send_counts), group=self.group)
+        return out.to(self.dev) if self.staged else out
 
     def send(self, table, counts, repeat=False):
         """Rows [off_p, off_p + counts[p]) of `table` go to rank p (every row
         to every rank when repeat); returns the rows this rank receives, in
         sender order.  Rows are packed on the GPU in the narrow wire layout
-        (capf_table_pack_rows) and moved by one all_to_all_single."""
-        cols, types, width, base, nullable = self._layout(table)
+        (capf_table_pack_rows) and moved by one all_to_all_single.  With LIST
+        columns: one more all-to-all for the element counts of all of them,
+        then one per LIST column for its element records
+        (capf_table_pack_list_elems), the slice of the stream that belongs to
+        the rows of each destination."""
+        cols, types, width, base, nullable, lists = self._layout(table)
         n = table.size
         k = len(cols)
         arrs = (_lib.strs(cols), (c_int32 * max(k, 1))(*width), (c_int64 * max(k, 1))(*base),
@@ -204,19 +299,55 @@ class GpuExchange:
         dist.all_to_all_single(recv_counts, send_counts, group=self.group)
         rc = recv_counts.tolist()
         m = sum(rc)
-        out = torch.empty((max(m, 1), W), dtype=torch.uint8, device=dev)[:m]
-        if W > 0:
-            src = rows.to(dev) if self.staged else rows
-            dist.all_to_all_single(out, src, rc, list(counts), group=self.group)
-        if self.staged:
-            out = out.to(self.dev)
+        out = self._all_to_all_rows(rows, counts, rc, dev)
+        elems = self._send_elements(table, counts, repeat, lists, dev) if lists else []
         torch.cuda.current_stream().synchronize()
         h = c_void_p()
         ty = (c_int32 * max(k, 1))(*types)
-        _lib.call("capf_table_from_packed_rows", self.s._h, k, arrs[0], ty, arrs[1], arrs[2], arrs[3],
-                  c_void_p(out.data_ptr() if m > 0 and W > 0 else 0), m, byref(h))
+        d_rows = c_void_p(out.data_ptr() if m > 0 and W > 0 else 0)
+        if not lists:
+            _lib.call("capf_table_from_packed_rows", self.s._h, k, arrs[0], ty, arrs[1], arrs[2], arrs[3], d_rows, m,
+                      byref(h))
+        else:
+            nl = len(lists)
+            _lib.call("capf_table_from_packed_lists", self.s._h, k, arrs[0], ty, arrs[1], arrs[2], arrs[3], d_rows, m,
+                      nl, (c_int32 * nl)(*[x[1] for x in lists]), (c_int32 * nl)(*[x[2] for x in lists]),
+                      (c_int64 * nl)(*[x[3] for x in lists]), (c_int32 * nl)(*[int(x[4]) for x in lists]),
+                      (c_void_p * nl)(*[e.data_ptr() if e.numel() else 0 for e in elems]),
+                      (c_int64 * nl)(*[e.shape[0] for e in elems]), byref(h))
         from .table import GpuTable
         return GpuTable(self.s, h)
+
+    def _send_elements(self, table, counts, repeat, lists, dev):
+        """The element records this rank receives, one (n_elems, record bytes)
+        tensor per LIST column.  The element counts per destination are
+        differences of the routed table's offsets (the whole stream for every
+        destination when repeat)."""
+        nl = len(lists)
+        packed, ecounts = [], []
+        slices = [table.size] if repeat else list(counts)
+        rc_arr = (c_int64 * len(slices))(*slices)
+        for col, et, ew, eb, en in lists:
+            ec = (c_int64 * len(slices))()
+            rec = c_int32()
+            args = (table._h, col.encode(), len(slices), rc_arr, et, ew, eb, int(en), ec, byref(rec))
+            _lib.call("capf_table_pack_list_elems", *args, None)
+            total = sum(ec)
+            buf = torch.empty(max(total * rec.value, 1), dtype=torch.uint8, device=self.dev)
+            _lib.call("capf_table_pack_list_elems", *args, c_void_p(buf.data_ptr()))
+            buf = buf[:total * rec.value].view(total, rec.value)
+            if repeat:
+                buf = buf.repeat(self.world, 1)
+            packed.append(buf)
+            ecounts.append([total] * self.world if repeat else list(ec))
+        # element counts of all LIST columns in one all-to-all: nl numbers per destination
+        send_ec = torch.tensor([ecounts[i][p] for p in range(self.world) for i in range(nl)], dtype=torch.int64,
+                               device=dev)
+        recv_ec = torch.empty_like(send_ec)
+        dist.all_to_all_single(recv_ec, send_ec, group=self.group)
+        recv_ec = recv_ec.view(self.world, nl).tolist()
+        return [self._all_to_all_rows(packed[i], ecounts[i], [recv_ec[p][i] for p in range(self.world)], dev)
+                for i in range(nl)]
 
 
 class DistSession:

@@ -728,7 +728,8 @@ capf_status capf_session_csv_slow_floats(capf_session *s, int64_t *out);
  *   owner = h(values of keys[0..nkeys)) of `parts` (owner order, stable inside
  *   an owner); counts[p] = rows owned by p (host array of `parts`).  Equal key
  *   tuples have equal owners; NULLs of a key route together; −0.0 as 0.0.
- *   LIST columns cannot be routed (CAPF_ERR_ILLEGAL_ARGUMENT).
+ *   LIST columns are carried along with their rows; a LIST column as a
+ *   routing key is refused (CAPF_ERR_ILLEGAL_ARGUMENT).
  * capf_table_download_device: `rows` of one column into DEVICE buffers
  *   (decoded values, size × 8 or 1 bytes; d_valid = size bytes, 1 = present).
  * capf_table_has_nulls: does column col carry a validity array (or is it
@@ -749,7 +750,51 @@ capf_status capf_table_has_nulls(capf_table *t, const char *col, int32_t *has);
  * INTEGER or STRING column (column statistics, computed once).
  * capf_table_pack_rows: *row_bytes = W; rows into d_out (n·W device bytes; null
  * d_out: only W).  capf_table_from_packed_rows: the table of nrows packed rows
- * at d_rows (copied out; the narrow widths stay FOR24 / FOR32 encoded).       */
+ * at d_rows (copied out; the narrow widths stay FOR24 / FOR32 encoded).
+ * DATE and LOCALDATETIME columns are packed like INTEGER columns.
+ *
+ * LIST columns.  Row part: a LIST column contributes a length field to the
+ * packed row — the list's element count little-endian, 0 for a NULL list —
+ * width[i] = 4 when the longest list over all ranks has fewer than 2^31
+ * elements, else 8 (base 0); then the usual validity byte when nullable[i].
+ * Element stream: the elements travel beside the rows as the packed rows of
+ * the child column taken as a one-column table, i.e. the record above for a
+ * scalar column of the element type: `width` bytes of (value − base) — 3 / 4
+ * for INTEGER and STRING-code elements whose range over all ranks fits 24 /
+ * 32 bits, 8 otherwise and for FLOAT, 1 for BOOLEAN, 0 for NULL-typed
+ * elements (only the lengths travel; the receiver rebuilds a NULL child of
+ * the summed length) — then one validity byte when an element is NULL on some
+ * rank.  The rows for rank p are a contiguous slice of the routed table, so
+ * its elements are the contiguous slice [off[r_p], off[r_p + counts[p]]) of
+ * the stream: the element send counts are differences of offsets.
+ * capf_table_pack_rows accepts LIST columns (width 4 or 8);
+ * capf_table_from_packed_rows does not (use capf_table_from_packed_lists).
+ * capf_table_list_stats: what the layout agreement needs of a LIST column:
+ *   element type, longest (non-NULL) list, element count, whether an element
+ *   is NULL, the element column's physical encoding (0 plain, 1 FOR32,
+ *   2 FOR24), and min / max / non-NULL count of INTEGER / STRING-code elements
+ *   (max < min: none).
+ * capf_table_pack_list_elems: the element stream of LIST column col for rows
+ *   split into nparts consecutive slices of row_counts[p] rows (they must sum
+ *   to the table's rows): elem_counts[p] = elements of slice p, *rec_bytes =
+ *   width + (elem_nullable ? 1 : 0), the records into d_out (Σ elem_counts ·
+ *   rec_bytes device bytes, 4-byte aligned, 8-byte for 8-byte records; null
+ *   d_out: sizes only).  A NULL list is empty on the wire: where a NULL list
+ *   owns elements in the column (capf_table_add_list accepts offsets that
+ *   give it some), they are left out of the stream and of the counts, here
+ *   and in capf_table_list_stats, so the receiver's NULL lists own none.  elem_type
+ *   is the agreed element type: the column's own, or any type when the
+ *   column's elements are NULL-typed (they are then sent as NULL elements of
+ *   that type and need the validity byte).
+ * capf_table_from_packed_lists: capf_table_from_packed_rows for rows with LIST
+ *   columns: the l-th LIST column (in column order) takes element stream l —
+ *   n_elems[l] records at d_elems[l] (4-byte aligned) of elem_width[l] bytes
+ *   (+ validity byte when elem_nullable[l]) of type elem_types[l].  The rows'
+ *   lengths must sum to n_elems[l].  The child keeps the narrow encoding.
+ * Bad arguments (counts that do not sum to the rows, a width that does not fit
+ * the element type, NULL elements without their validity byte, a LIST column
+ * named where a scalar is expected or the reverse) are
+ * CAPF_ERR_ILLEGAL_ARGUMENT.                                                  */
 capf_status capf_table_column_range(capf_table *t, const char *col, int64_t *min, int64_t *max,
                                     int64_t *non_null);
 capf_status capf_table_pack_rows(capf_table *t, int32_t ncols, const char *const *cols, const int32_t *width,
@@ -758,6 +803,18 @@ capf_status capf_table_from_packed_rows(capf_session *s, int32_t ncols, const ch
                                         const int32_t *types, const int32_t *width, const int64_t *base,
                                         const int32_t *nullable, const void *d_rows, int64_t nrows,
                                         capf_table **out);
+capf_status capf_table_list_stats(capf_table *t, const char *col, int32_t *elem_type, int64_t *longest,
+                                  int64_t *n_elems, int32_t *elem_nulls, int32_t *elem_enc, int64_t *min,
+                                  int64_t *max, int64_t *non_null);
+capf_status capf_table_pack_list_elems(capf_table *t, const char *col, int32_t nparts, const int64_t *row_counts,
+                                       int32_t elem_type, int32_t width, int64_t base, int32_t elem_nullable,
+                                       int64_t *elem_counts, int32_t *rec_bytes, void *d_out);
+capf_status capf_table_from_packed_lists(capf_session *s, int32_t ncols, const char *const *names,
+                                         const int32_t *types, const int32_t *width, const int64_t *base,
+                                         const int32_t *nullable, const void *d_rows, int64_t nrows, int32_t nlists,
+                                         const int32_t *elem_types, const int32_t *elem_width,
+                                         const int64_t *elem_base, const int32_t *elem_nullable,
+                                         const void *const *d_elems, const int64_t *n_elems, capf_table **out);
 
 /* ------------------------------------------------- rank communicator (RCCL)
  * The exchange of the distributed Table layer for hosts without a framework

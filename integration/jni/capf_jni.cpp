@@ -850,6 +850,67 @@ JNI(jlong, tableFromPackedRows)(JNIEnv *env, jobject, jlong s, jobjectArray name
     return 0;
   return H(out);
 }
+// LIST columns on the wire (capf_gpu.h "LIST columns"): every buffer is a Java
+// array (length-checked here) or a device address; no direct buffer is taken.
+// out = {elem_type, longest, n_elems, elem_nulls, elem_enc, min, max, non_null}
+JNI(void, tableListStats)(JNIEnv *env, jobject, jlong t, jstring col, jlongArray out) {
+  JStr c(env, col);
+  if (!out || env->GetArrayLength(out) < 8) {
+    illegal_argument(env, "tableListStats: out needs 8 entries");
+    return;
+  }
+  int32_t et = 0, en = 0, enc = 0;
+  int64_t longest = 0, ne = 0, mn = 0, mx = 0, nn = 0;
+  if (fail(env, capf_table_list_stats(T(t), c.p, &et, &longest, &ne, &en, &enc, &mn, &mx, &nn))) return;
+  jlong v[8] = {(jlong)et, (jlong)longest, (jlong)ne, (jlong)en, (jlong)enc, (jlong)mn, (jlong)mx, (jlong)nn};
+  env->SetLongArrayRegion(out, 0, 8, v);
+}
+// returns the record bytes; elemCountsOut[0..rowCounts.length) = elements per slice; d_out = 0: sizes only
+JNI(jint, tablePackListElems)(JNIEnv *env, jobject, jlong t, jstring col, jlongArray rowCounts, jint elemType,
+                              jint width, jlong base, jint elemNullable, jlongArray elemCountsOut, jlong d_out) {
+  JStr c(env, col);
+  const std::vector<int64_t> rc = longs(env, rowCounts);
+  if (rc.empty() || !elemCountsOut || (size_t)env->GetArrayLength(elemCountsOut) < rc.size()) {
+    illegal_argument(env, "tablePackListElems: rowCounts and elemCountsOut need one entry per destination");
+    return 0;
+  }
+  std::vector<int64_t> ec(rc.size(), 0);
+  int32_t rec = 0;
+  if (fail(env, capf_table_pack_list_elems(T(t), c.p, (int32_t)rc.size(), rc.data(), elemType, width, base,
+                                           elemNullable, ec.data(), &rec, reinterpret_cast<void *>(d_out))))
+    return 0;
+  std::vector<jlong> v(ec.begin(), ec.end());
+  env->SetLongArrayRegion(elemCountsOut, 0, (jsize)v.size(), v.data());
+  return rec;
+}
+JNI(jlong, tableFromPackedLists)(JNIEnv *env, jobject, jlong s, jobjectArray names, jintArray types,
+                                 jintArray width, jlongArray base, jintArray nullable, jlong d_rows, jlong nrows,
+                                 jintArray elemTypes, jintArray elemWidth, jlongArray elemBase,
+                                 jintArray elemNullable, jlongArray dElems, jlongArray nElems) {
+  JStrs nm(env, names);
+  std::vector<int32_t> ty = ints(env, types), w = ints(env, width), nl = ints(env, nullable);
+  std::vector<int64_t> b = longs(env, base);
+  if ((int64_t)ty.size() != nm.n() || (int64_t)w.size() != nm.n() || (int64_t)b.size() != nm.n() ||
+      (int64_t)nl.size() != nm.n()) {
+    illegal_argument(env, "tableFromPackedLists: types, width, base and nullable need one entry per column");
+    return 0;
+  }
+  std::vector<int32_t> et = ints(env, elemTypes), ew = ints(env, elemWidth), en = ints(env, elemNullable);
+  std::vector<int64_t> eb = longs(env, elemBase), de = longs(env, dElems), ne = longs(env, nElems);
+  const size_t k = et.size();
+  if (ew.size() != k || en.size() != k || eb.size() != k || de.size() != k || ne.size() != k) {
+    illegal_argument(env, "tableFromPackedLists: the element arrays need one entry per LIST column");
+    return 0;
+  }
+  std::vector<const void *> ptrs(k);
+  for (size_t i = 0; i < k; ++i) ptrs[i] = reinterpret_cast<const void *>(de[i]);
+  capf_table *out = nullptr;
+  if (fail(env, capf_table_from_packed_lists(S(s), nm.n(), nm.data(), ty.data(), w.data(), b.data(), nl.data(),
+                                             reinterpret_cast<const void *>(d_rows), nrows, (int32_t)k, et.data(),
+                                             ew.data(), eb.data(), en.data(), ptrs.data(), ne.data(), &out)))
+    return 0;
+  return H(out);
+}
 JNI(void, tableDownloadDevice)(JNIEnv *env, jobject, jlong t, jstring col, jlong d_values,
                                jlong d_valid) {
   JStr c(env, col);

@@ -84,23 +84,32 @@ final class GpuRankContext(val session: GpuCypherSession, val comm: Long) extend
   }
 
   // ------------------------------------------------------------------ rows
-  /** Rows of `t` grouped by owner h(keys) (capf_table_hash_route) and the count per owner. */
+  /** Rows of `t` grouped by owner h(keys) (capf_table_hash_route) and the count per owner.
+    * LIST columns are carried along but never route: only the other keys are passed
+    * (a subset of a key tuple routes correctly). */
   def route(t: GpuTable, keys: Seq[String]): (GpuTable, Array[Long]) = {
     val counts = new Array[Long](world)
-    val h = Native.guard(Native.tableHashRoute(t.handle, keys.take(8).toArray, world, counts))
+    val scalar = keys.filter(k => Native.guard(Native.tableColumnType(t.handle, k)) != Native.TypeList)
+    val h = Native.guard(Native.tableHashRoute(t.handle, scalar.take(8).toArray, world, counts))
     (GpuTable(h)(session), counts)
   }
 
-  def shuffle(t: GpuTable, keys: Seq[String]): GpuTable = {
-    val (routed, counts) = route(t, keys)
-    send(routed, counts, repeat = false)
-  }
+  def shuffle(t: GpuTable, keys: Seq[String]): GpuTable =
+    if (keys.forall(k => Native.guard(Native.tableColumnType(t.handle, k)) == Native.TypeList))
+      toRoot(t) // no routable key: the rows meet on rank 0
+    else {
+      val (routed, counts) = route(t, keys)
+      send(routed, counts, repeat = false)
+    }
 
   /** The rows this rank owns of a table every rank holds in full (ingest sharding, no exchange). */
-  def ownShare(t: GpuTable, keys: Seq[String]): GpuTable = {
-    val (routed, counts) = route(t, keys)
-    routed.skip(counts.take(rank).sum).limit(counts(rank)).cache()
-  }
+  def ownShare(t: GpuTable, keys: Seq[String]): GpuTable =
+    if (keys.forall(k => Native.guard(Native.tableColumnType(t.handle, k)) == Native.TypeList))
+      if (rank == 0) t else t.limit(0) // no routable key: rank 0 keeps every row
+    else {
+      val (routed, counts) = route(t, keys)
+      routed.skip(counts.take(rank).sum).limit(counts(rank)).cache()
+    }
 
   def toRoot(t: GpuTable): GpuTable = {
     val n = t.size
@@ -109,79 +118,175 @@ final class GpuRankContext(val session: GpuCypherSession, val comm: Long) extend
 
   def replicate(t: GpuTable): GpuTable = send(t, Array.fill(world)(t.size), repeat = true)
 
+  /** The element layout of one LIST column: agreed element type, record width, base, validity byte. */
+  private final case class ListWire(col: String, elemType: Int, width: Int, base: Long, nullable: Int) {
+    def rec: Int = width + nullable
+  }
+
+  private def isIntPayload(ty: Int): Boolean =
+    ty == Native.TypeInt64 || ty == Native.TypeString || ty == Native.TypeDate || ty == Native.TypeLocalDateTime
+
+  /** One rank's (−min, max) entries of the layout all-reduce (dist_table.py range_entries): no value
+    * sends the lowest pair; −Long.MinValue wraps, so a minimum of Long.MinValue sends (big, big) and
+    * the agreed range is wider than 2^32 on every rank: the plain 8 bytes. */
+  private def rangeEntries(mn: Long, mx: Long, nonNull: Long): (Long, Long) =
+    if (nonNull <= 0) (-Long.MaxValue, -Long.MaxValue)
+    else if (mn == Long.MinValue) (Long.MaxValue, Long.MaxValue)
+    else (-mn, mx)
+
+  /** Per LIST column in the layout all-reduce: type, longest, NULL flag, −min, max, −type. */
+  private val ListEntries = 6
+
+  /** (width, base) of one value of type `ty` whose integer payload spans [gmin, gmax] over all ranks. */
+  private def scalarWire(ty: Int, gmin: Long, gmax: Long): (Int, Long) = ty match {
+    case Native.TypeNull => (0, 0L)
+    case Native.TypeBool => (1, 0L)
+    case _ if isIntPayload(ty) =>
+      if (gmax < gmin) (3, 0L)
+      else if (gmax - gmin >= 0 && gmax - gmin < (1L << 24)) (3, gmin)
+      else if (gmax - gmin >= 0 && gmax - gmin < (1L << 32)) (4, gmin)
+      else (8, 0L)
+    case _ => (8, 0L)
+  }
+
   /** The wire layout every rank agrees on in ONE max all-reduce (dist_table.py
     * GpuExchange._layout): per column the width of (value − base) — 3 / 4 where
-    * the range over all ranks fits 24 / 32 bits — and a validity byte where
-    * some rank has NULLs; STRING codes need equal dictionaries (digest check). */
-  private def layout(t: GpuTable): (Array[String], Array[Int], Array[Int], Array[Long], Array[Int]) = {
+    * the range over all ranks fits 24 / 32 bits, DATE and LOCALDATETIME like
+    * INTEGER — and a validity byte where some rank has NULLs; STRING codes (in a
+    * column or as list elements) need equal dictionaries (digest check); per LIST
+    * column the element type (NULL = 0 lowest), the longest list, the element NULL
+    * flag, −min / max of INTEGER / STRING elements and −type (capf_table_list_stats). */
+  private def layout(t: GpuTable): (Array[String], Array[Int], Array[Int], Array[Long], Array[Int], Seq[ListWire]) = {
     val cols = t.physicalColumns.toArray
     val types = cols.map(c => Native.guard(Native.tableColumnType(t.handle, c)))
-    if (types.contains(Native.TypeList)) throw NotImplementedException("LIST columns are not moved between ranks")
     val k = cols.length
     val big = Long.MaxValue
     val has = cols.map(c => if (Native.guard(Native.tableHasNulls(t.handle, c))) 1L else 0L)
     val ranges = cols.zip(types).map { case (c, ty) =>
-      if (ty == Native.TypeInt64 || ty == Native.TypeString) {
+      if (isIntPayload(ty)) {
         val r = new Array[Long](3)
         Native.guard(Native.tableColumnRange(t.handle, c, r))
-        if (r(2) > 0) (-r(0), r(1)) else (-big, -big)
+        rangeEntries(r(0), r(1), r(2))
       } else (-big, -big)
     }
+    val listCols = cols.zip(types).collect { case (c, Native.TypeList) => c }
+    val listStats = listCols.flatMap { c =>
+      val r = new Array[Long](8) // elem type, longest, n_elems, elem nulls, enc, min, max, non-null
+      Native.guard(Native.tableListStats(t.handle, c, r))
+      val (negMin, mx) = rangeEntries(r(5), r(6), r(7))
+      Array(r(0), r(1), r(3), negMin, mx, if (r(0) != Native.TypeNull) -r(0) else -big)
+    }
     val check =
-      if (!types.contains(Native.TypeString)) Array.empty[Long]
+      if (!types.contains(Native.TypeString) && listCols.isEmpty) Array.empty[Long]
       else {
         val d = new Array[Long](2)
         Native.guard(Native.stringDigest(session.handle, d))
         Array(d(0), -d(0), d(1), if (d(1) == Long.MinValue) big else -d(1))
       }
-    val got = allReduce(has ++ ranges.map(_._1) ++ ranges.map(_._2) ++ check, Native.CommMax)
-    if (check.nonEmpty) {
+    val got = allReduce(has ++ ranges.map(_._1) ++ ranges.map(_._2) ++ check ++ listStats, Native.CommMax)
+    val l0 = 3 * k + check.length
+    val elemTypes = listCols.indices.map(i => got(l0 + ListEntries * i).toInt)
+    listCols.indices.foreach { i =>
+      // the ranks' non-NULL element types must be equal: raised on every rank before any further collective
+      val low = got(l0 + ListEntries * i + 5)
+      if (low != -big && -low != elemTypes(i))
+        throw IllegalStateException(s"LIST column '${listCols(i)}' holds elements of different types on " +
+          s"different ranks (types ${-low} and ${elemTypes(i)}): it cannot be exchanged")
+    }
+    if (check.nonEmpty && (types.contains(Native.TypeString) || elemTypes.contains(Native.TypeString))) {
       val c0 = 3 * k
       if (got(c0) != -got(c0 + 1) || (got(c0 + 2) != -got(c0 + 3) && check(2) != Long.MinValue))
         throw IllegalStateException("string dictionaries differ between ranks: STRING columns cannot move as codes")
     }
     val nullable = Array.tabulate(k)(j => if (got(j) != 0 && types(j) != Native.TypeNull) 1 else 0)
+    val lists = listCols.indices.map { i =>
+      val g = got.slice(l0 + ListEntries * i, l0 + ListEntries * i + 5)
+      val (ew, eb) = scalarWire(g(0).toInt, -g(3), g(4))
+      ListWire(listCols(i), g(0).toInt, ew, eb, if (g(2) != 0 && g(0) != Native.TypeNull) 1 else 0)
+    }
+    var li = -1
     val (width, base) = Array.tabulate(k) { j =>
-      types(j) match {
-        case Native.TypeNull => (0, 0L)
-        case Native.TypeBool => (1, 0L)
-        case Native.TypeInt64 | Native.TypeString =>
-          val (gmin, gmax) = (-got(k + j), got(2 * k + j))
-          if (gmax < gmin) (3, 0L)
-          else if (gmax - gmin < (1L << 24)) (3, gmin)
-          else if (gmax - gmin < (1L << 32)) (4, gmin)
-          else (8, 0L)
-        case _ => (8, 0L)
-      }
+      if (types(j) == Native.TypeList) {
+        li += 1
+        (if (got(l0 + ListEntries * li + 1) < (1L << 31)) 4 else 8, 0L) // the length field
+      } else scalarWire(types(j), -got(k + j), got(2 * k + j))
     }.unzip
-    (cols, types, width, base, nullable)
+    (cols, types, width, base, nullable, lists)
+  }
+
+  /** `counts` to every rank, theirs back: the counts all-to-all as one all-gather. */
+  private def exchangeCounts(counts: Array[Long]): Array[Long] = allGather(counts).map(_(rank))
+
+  /** One all-to-all of `w`-byte records: sendCounts(p) records to rank p; the receive buffer (the caller frees it). */
+  private def allToAllRecords(sendBuf: Long, w: Long, sendCounts: Array[Long], recvCounts: Array[Long]): Long = {
+    val recv = Native.guard(Native.sessionAlloc(s, math.max(recvCounts.sum * w, 1L)))
+    if (w > 0) Native.guard(Native.commAllToAllBytes(comm, sendBuf, sendCounts.map(_ * w), recv, recvCounts.map(_ * w)))
+    recv
   }
 
   /** Rows [off_p, off_p + counts(p)) of `t` go to rank p (every row to every
     * rank when `repeat`); the rows this rank receives, in sender order, packed
-    * on the GPU (capf_table_pack_rows) and moved by one all-to-all. */
+    * on the GPU (capf_table_pack_rows) and moved by one all-to-all.  With LIST
+    * columns: one more counts exchange for the element counts of all of them,
+    * then one all-to-all per LIST column for its element records
+    * (capf_table_pack_list_elems), and capf_table_from_packed_lists. */
   def send(t: GpuTable, counts: Array[Long], repeat: Boolean): GpuTable = {
-    val (cols, types, width, base, nullable) = layout(t)
+    val (cols, types, width, base, nullable, lists) = layout(t)
     val n = t.size
     val w = width.sum + nullable.sum
-    val packed = Native.guard(Native.sessionAlloc(s, math.max(n * w, 1L)))
-    val sendBuf = if (repeat) Native.guard(Native.sessionAlloc(s, math.max(n * w * world, 1L))) else packed
+    var owned = List.empty[Long]
+    def alloc(bytes: Long): Long = {
+      val p = Native.guard(Native.sessionAlloc(s, math.max(bytes, 1L)))
+      owned ::= p
+      p
+    }
+    /** `bytes` packed once, `world` copies when repeat. */
+    def repeated(packed: Long, bytes: Long): Long =
+      if (!repeat) packed
+      else {
+        val all = alloc(bytes * world)
+        (0 until world).foreach(p => Native.guard(Native.sessionCopyDevice(s, all + p * bytes, packed, bytes)))
+        all
+      }
     try {
+      val packed = alloc(n * w)
       val wb = Native.guard(Native.tablePackRows(t.handle, cols, width, base, nullable, packed))
       require(wb == w, s"packed row width $wb, expected $w")
-      if (repeat) (0 until world).foreach(p => Native.guard(Native.sessionCopyDevice(s, sendBuf + p * n * w, packed, n * w)))
-      val recvCounts = allGather(counts).map(_(rank))
+      val sendBuf = repeated(packed, n * w)
+      val recvCounts = exchangeCounts(counts)
       val m = recvCounts.sum
-      val recv = Native.guard(Native.sessionAlloc(s, math.max(m * w, 1L)))
-      try {
-        if (w > 0) Native.guard(Native.commAllToAllBytes(comm, sendBuf, counts.map(_ * w), recv, recvCounts.map(_ * w)))
-        GpuTable(Native.guard(Native.tableFromPackedRows(s, cols, types, width, base, nullable,
-          if (m > 0 && w > 0) recv else 0L, m)))(session)
-      } finally Native.guard(Native.sessionFree(s, recv))
-    } finally {
-      Native.guard(Native.sessionFree(s, packed))
-      if (repeat) Native.guard(Native.sessionFree(s, sendBuf))
-    }
+      val recv = allToAllRecords(sendBuf, w, counts, recvCounts)
+      owned ::= recv
+      val dRows = if (m > 0 && w > 0) recv else 0L
+      if (lists.isEmpty)
+        GpuTable(Native.guard(Native.tableFromPackedRows(s, cols, types, width, base, nullable, dRows, m)))(session)
+      else {
+        val slices = if (repeat) Array(n) else counts
+        val sent = lists.map { l =>
+          val ec = new Array[Long](slices.length)
+          val rec = Native.guard(Native.tablePackListElems(t.handle, l.col, slices, l.elemType, l.width, l.base,
+            l.nullable, ec, 0L))
+          require(rec == l.rec, s"packed element record $rec bytes, expected ${l.rec}")
+          val total = ec.sum
+          val buf = alloc(total * rec)
+          Native.guard(Native.tablePackListElems(t.handle, l.col, slices, l.elemType, l.width, l.base, l.nullable,
+            ec, buf))
+          (repeated(buf, total * rec), if (repeat) Array.fill(world)(total) else ec)
+        }
+        // the element counts of all LIST columns in one exchange: lists.length numbers per destination
+        val nl = lists.length
+        val theirs = allGather(Array.tabulate(world * nl)(i => sent(i % nl)._2(i / nl)))
+        val streams = lists.indices.map { i =>
+          val rc = Array.tabulate(world)(p => theirs(p)(rank * nl + i))
+          val buf = allToAllRecords(sent(i)._1, lists(i).rec, sent(i)._2, rc)
+          owned ::= buf
+          (if (rc.sum > 0 && lists(i).rec > 0) buf else 0L, rc.sum)
+        }
+        GpuTable(Native.guard(Native.tableFromPackedLists(s, cols, types, width, base, nullable, dRows, m,
+          lists.map(_.elemType).toArray, lists.map(_.width).toArray, lists.map(_.base).toArray,
+          lists.map(_.nullable).toArray, streams.map(_._1).toArray, streams.map(_._2).toArray)))(session)
+      }
+    } finally owned.foreach(p => Native.guard(Native.sessionFree(s, p)))
   }
 
   override def close(): Unit = {

@@ -279,6 +279,18 @@ object Native {
                             nullable: Array[Int], dOut: Long): Int
   @native def tableFromPackedRows(session: Long, names: Array[String], types: Array[Int], width: Array[Int],
                                   base: Array[Long], nullable: Array[Int], dRows: Long, nrows: Long): Long
+  // LIST columns on the wire (capf_gpu.h "LIST columns").  tableListStats: out = {elem type, longest list,
+  // element count, element NULL flag, element encoding, min, max, non-NULL count};  tablePackListElems
+  // returns the record bytes (dOut = 0: sizes only) and fills elemCountsOut per destination;
+  // tableFromPackedLists takes one element stream (device address, record count) per LIST column, in
+  // column order.
+  @native def tableListStats(table: Long, col: String, out: Array[Long]): Unit
+  @native def tablePackListElems(table: Long, col: String, rowCounts: Array[Long], elemType: Int, width: Int,
+                                 base: Long, elemNullable: Int, elemCountsOut: Array[Long], dOut: Long): Int
+  @native def tableFromPackedLists(session: Long, names: Array[String], types: Array[Int], width: Array[Int],
+                                   base: Array[Long], nullable: Array[Int], dRows: Long, nrows: Long,
+                                   elemTypes: Array[Int], elemWidth: Array[Int], elemBase: Array[Long],
+                                   elemNullable: Array[Int], dElems: Array[Long], nElems: Array[Long]): Long
 
   // rank communicator (RCCL over xGMI, capf_comm_*) and session device buffers
   final val CommSum = 0
