@@ -622,6 +622,10 @@ int32_t record_error(int32_t code, const char *msg);
 
 // Fused counting over lazy inner-join trees (the Expand hot path).
 bool try_fused_count(const NodePtr &n, int64_t *out);
+// group(keys; count(*)) over an inner-join tree, the keys columns of one leaf
+// (or literals): message passing with that leaf as root and one weight per
+// row, no joined row materialised (fused_count.hip); false: not that shape.
+bool try_fused_group_count(const NodePtr &grp, DataPtr &out);
 // Config 5 below the SPI: Group(a; count(*)) over Distinct(a, b) over the
 // UNION ALL of the var-length join chains k = 1..u (reach_plan.hip) →
 // the (a-keys, reach) rows by multi-source BFS; chains k = l..u with

@@ -273,6 +273,105 @@ __global__ void k_add_u64(unsigned long long *acc, unsigned long long v) {
   if (threadIdx.x == 0) atomicAdd(acc, v);
 }
 
+// ============================================================ root by rows
+// The grouped count (try_fused_group_count): the root keeps one weight per row
+// instead of their sum.  Row r's weight goes to acc[r] — written by the first
+// inclusion–exclusion term (ROWS_SET), added or subtracted by the later ones
+// (exact modulo 2^64; a partial sum may pass below zero, the final one does
+// not).  A row belongs to one thread and the terms run in stream order: no
+// atomics.
+enum RowsMode : int32_t { ROWS_SET = 0, ROWS_ADD = 1, ROWS_SUB = 2 };
+
+__device__ inline unsigned long long rows_apply(unsigned long long old, unsigned long long w, int mode) {
+  return mode == ROWS_ADD ? old + w : old - w;
+}
+
+__global__ __launch_bounds__(256) void k_message_rows(const MsgJob j, int64_t n, unsigned long long *acc,
+                                                      int mode) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n;
+       r += (int64_t)gridDim.x * blockDim.x) {
+    unsigned long long w = 1;
+    for (int c = 0; c < j.nchild && w; ++c) {
+      int64_t k;
+      w = load_key(j.cols[c], r, k) ? w * map_get(j.child[c], k) : 0ull;
+    }
+    if (mode == ROWS_SET)
+      acc[r] = w;
+    else if (w)
+      acc[r] = rows_apply(acc[r], w, mode);
+  }
+}
+
+// The root by rows with ONE remaining 0/1 child message over a non-null key
+// column (k_message_root1's case): 4 rows per 12/16-B load (FOR24 / FOR32) or
+// two 16-B loads (int64), 8 rows in flight per lane, each lane's 4 weights
+// stored as two 16-B words (a wave writes 2 KiB contiguous).
+template <int W>
+__device__ inline void rows1_keys(const ColView &c, int64_t g, int64_t k[4]) {
+  if (W == 4) {
+    const uint4 a = ((const uint4 *)c.data)[g];
+    k[0] = c.base + (int64_t)a.x, k[1] = c.base + (int64_t)a.y;
+    k[2] = c.base + (int64_t)a.z, k[3] = c.base + (int64_t)a.w;
+  } else if (W == 3) {
+    const U3w a = *(const U3w *)((const uint8_t *)c.data + 12 * g);
+    k[0] = c.base + (int64_t)(a.x & 0xFFFFFFu);
+    k[1] = c.base + (int64_t)(__builtin_amdgcn_alignbit(a.y, a.x, 24) & 0xFFFFFFu);
+    k[2] = c.base + (int64_t)(__builtin_amdgcn_alignbit(a.z, a.y, 16) & 0xFFFFFFu);
+    k[3] = c.base + (int64_t)(a.z >> 8);
+  } else {
+    const longlong2 *p = (const longlong2 *)c.data;
+    const longlong2 a0 = p[2 * g], a1 = p[2 * g + 1];
+    k[0] = a0.x, k[1] = a0.y, k[2] = a1.x, k[3] = a1.y;
+  }
+}
+
+__device__ inline void rows1_store(unsigned long long *acc, int64_t g, const unsigned long long w[4], int mode) {
+  ulonglong2 *p = (ulonglong2 *)(acc + 4 * g);
+  if (mode == ROWS_SET) {
+    p[0] = make_ulonglong2(w[0], w[1]);
+    p[1] = make_ulonglong2(w[2], w[3]);
+  } else if (w[0] | w[1] | w[2] | w[3]) {
+    const ulonglong2 a = p[0], b = p[1];
+    p[0] = make_ulonglong2(rows_apply(a.x, w[0], mode), rows_apply(a.y, w[1], mode));
+    p[1] = make_ulonglong2(rows_apply(b.x, w[2], mode), rows_apply(b.y, w[3], mode));
+  }
+}
+
+template <int KA, int W>
+__global__ __launch_bounds__(256) void k_message_rows1(const ColView c, const DMap m, int64_t n,
+                                                       unsigned long long *acc, int mode) {
+  const int64_t groups = n / 4, T = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += 2 * T) {
+    const int64_t g2 = g + T < groups ? g + T : g;
+    int64_t ka[4], kb[4];
+    rows1_keys<W>(c, g, ka);
+    rows1_keys<W>(c, g2, kb);
+    unsigned long long wa[4], wb[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      wa[u] = map_get_t<KA, 0>(m, ka[u]);
+      wb[u] = map_get_t<KA, 0>(m, kb[u]);
+    }
+    rows1_store(acc, g, wa, mode);
+    if (g2 != g) rows1_store(acc, g2, wb, mode);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (unsigned)(n - 4 * groups)) {  // ragged tail
+    const int64_t r = 4 * groups + threadIdx.x;
+    const unsigned long long w = map_get(m, ld_int(c, r));
+    if (mode == ROWS_SET)
+      acc[r] = w;
+    else if (w)
+      acc[r] = rows_apply(acc[r], w, mode);
+  }
+}
+
+// flag[r] = the row's final weight is not zero (the rows of the grouped result)
+__global__ void k_rows_nonzero(const unsigned long long *acc, int64_t n, uint8_t *flag) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n;
+       r += (int64_t)gridDim.x * blockDim.x)
+    flag[r] = acc[r] != 0;
+}
+
 // ============================================================ 2-hop fast path
 // One pass over the rel table computes, for the Sb key range [lo, hi]:
 //   h1[b] += Wa(u1)        for rels with v1 = b      (hop 1, message R1 → S_b)
@@ -933,7 +1032,20 @@ static const char *kind_token(int kind) {
 // Adds the join tree's count to the device counter *d_acc (no host wait).
 // Appends one token per step to `detail` (host side; capf_session_last_plan_detail):
 // the kind of every message sent, then the root's kernel.
-static bool tree_count(Session *s, JoinGraph &g, unsigned long long *d_acc, std::string &detail) {
+//
+// `rows` given (the grouped count): the root is the caller's leaf, its rows
+// materialised once by the caller and shared by every term, and each row's
+// weight goes to rows->acc[row] instead of the sum to *d_acc.  The messages
+// below the root are the same either way.
+struct RowsOut {
+  int root;                 // the group leaf's index in g
+  LeafData data;            // its rows
+  unsigned long long *acc;  // uint64 [rows]
+  int mode;                 // RowsMode: set (first term), add, subtract
+};
+
+static bool tree_count(Session *s, JoinGraph &g, unsigned long long *d_acc, std::string &detail,
+                       const RowsOut *rows = nullptr) {
   const int L = (int)g.leaves.size();
   if (L == 0) return false;
   auto token = [&](const std::string &t) {
@@ -977,11 +1089,12 @@ static bool tree_count(Session *s, JoinGraph &g, unsigned long long *d_acc, std:
       root = r;
     }
   }
+  if (rows) root = rows->root;
   // a node with more joined tables than a job holds: the joins materialise
   for (int v = 0; v < L; ++v)
     if ((int)adj[v].size() - (v == root ? 0 : 1) > MAX_CHILD) return false;
   std::vector<LeafData> data(L);
-  for (int i = 0; i < L; ++i) data[i] = leaf_data(g.leaves[i]);
+  for (int i = 0; i < L; ++i) data[i] = rows && i == root ? rows->data : leaf_data(g.leaves[i]);
   for (int i = 0; i < L; ++i)
     if (data[i].data->nrows >= (int64_t(1) << 40)) return false;
 
@@ -1023,6 +1136,39 @@ static bool tree_count(Session *s, JoinGraph &g, unsigned long long *d_acc, std:
         }
       }
       j.nchild = keep;
+    }
+    if (parent < 0 && rows) {
+      // the root by rows: rows_all (no child left: every row weighs 1 — the
+      // row kernel without a child is the fill), rows1 (one 0/1 child over a
+      // non-null, 16-B aligned key column), rows:<nchild>
+      const bool one = j.nchild == 1 && j.cols[0].data && !j.cols[0].valid &&
+                       ((uintptr_t)j.cols[0].data & 15) == 0 &&
+                       (j.child[0].kind == MAP_BITS || j.child[0].kind == MAP_ONES);
+      const int cw = !one ? 0 : j.cols[0].enc == ENC_FOR32 ? 4 : j.cols[0].enc == ENC_FOR24 ? 3 : 8;
+      token(j.nchild == 0 ? std::string("rows_all")
+            : one         ? std::string("rows1:") + kind_token(j.child[0].kind) + ":w" + std::to_string(cw)
+                          : "rows:" + std::to_string(j.nchild));
+      if (n == 0) return;
+      if (one) {
+        KernelTimer kt(s, "message_rows", (double)(cw + (rows->mode == ROWS_SET ? 8 : 16)) * n);
+        auto pick = [&](auto ka) {
+          constexpr int KA = decltype(ka)::value;
+          return cw == 4 ? k_message_rows1<KA, 4> : cw == 3 ? k_message_rows1<KA, 3> : k_message_rows1<KA, 8>;
+        };
+        auto kern = j.child[0].kind == MAP_BITS ? pick(std::integral_constant<int, MAP_BITS>())
+                                                : pick(std::integral_constant<int, MAP_ONES>());
+        hipLaunchKernelGGL(kern, dim3(grid_for(n / 8 + 1, 256, (int64_t)s->num_cus * 16)), dim3(256), 0,
+                           s->stream, j.cols[0], j.child[0], n, rows->acc, rows->mode);
+      } else {
+        KernelTimer kt(s, "message_rows", 8.0 * n * (j.nchild + (rows->mode == ROWS_SET ? 1 : 2)));
+        hipLaunchKernelGGL(k_message_rows, dim3(grid_for(n, 256)), dim3(256), 0, s->stream, j, n, rows->acc,
+                           rows->mode);
+      }
+      KERNEL_CHECK();
+      return;
+    }
+    if (parent < 0 && data[v].plain) {
+      const int keep = j.nchild;
       if (keep == 0) {  // every row counts once
         token("all_rows");
         if (n > 0) hipLaunchKernelGGL(k_add_u64, dim3(1), dim3(64), 0, s->stream, d_acc, (unsigned long long)n);
@@ -1190,7 +1336,11 @@ static void contract_pair(JoinGraph &g, int A, int B, std::vector<std::pair<ColR
   ++g.pair_joins;
 }
 
-static bool apply_equalities(const JoinGraph &g, const std::vector<int> &subset, JoinGraph &out) {
+// `track` (optional): a leaf of g on entry, the same leaf's index in `out` on
+// return — or −1 when it was merged with another scan or contracted into a
+// pair join (then it no longer has its own rows).
+static bool apply_equalities(const JoinGraph &g, const std::vector<int> &subset, JoinGraph &out,
+                             int *track = nullptr) {
   const int L = (int)g.leaves.size();
   std::vector<int> rep(L);
   std::iota(rep.begin(), rep.end(), 0);
@@ -1257,10 +1407,20 @@ static bool apply_equalities(const JoinGraph &g, const std::vector<int> &subset,
     }
     if (!merged) out.eqs.emplace_back(a, b);
   }
-  while (!extra.empty()) {
-    const int A = extra[0].first.leaf, B = extra[0].second.leaf;
-    contract_pair(out, std::min(A, B), std::max(A, B), extra);
+  int t = -1;
+  if (track) {
+    int members = 0;
+    for (int i = 0; i < L; ++i) members += find(i) == find(*track) ? 1 : 0;
+    t = members == 1 ? newid[*track] : -1;
   }
+  while (!extra.empty()) {
+    const int A = std::min(extra[0].first.leaf, extra[0].second.leaf);
+    const int B = std::max(extra[0].first.leaf, extra[0].second.leaf);
+    contract_pair(out, A, B, extra);
+    if (t == A || t == B) t = -1;
+    else if (t > B) --t;
+  }
+  if (track) *track = t;
   return true;
 }
 
@@ -1720,6 +1880,147 @@ bool try_fused_count(const NodePtr &n, int64_t *out) {
   HIP_CHECK(hipMemcpyAsync(s->h_scalars, dst, 8, hipMemcpyDeviceToHost, s->stream));
   s->sync();
   *out = (int64_t)s->h_scalars[0];
+  return true;
+}
+
+// ============================================================ grouped count
+// group(keys; count(*)) over an inner-join tree whose keys are columns of ONE
+// leaf G (and literal columns): G is the root of every inclusion–exclusion
+// term and keeps one weight per row — the count of the joined rows that row
+// takes part in.  G is in no uniqueness predicate, so no term merges it: the
+// same rows, materialised once, in every term.  Rows of weight 0 have no
+// joined row and no group (an inner join).  Then
+//   group:unique  a key column of G is non-null and pairwise distinct: every
+//                 surviving row is its own group — keys gathered lazily over
+//                 the row index, count = the weight, rows in G's order;
+//   group:hash    otherwise: the existing grouping over (G's keys, weight) of
+//                 the surviving rows, SUM over the weight.
+bool try_fused_group_count(const NodePtr &grp, DataPtr &result) {
+  const char *fe = getenv("CAPF_FUSED_GROUP");  // 0: always the relational plan
+  if (fe && atoi(fe) == 0) return false;
+  if (grp->kind != Kind::Group || grp->key_index.empty() || grp->aggs.empty()) return false;
+  for (auto &a : grp->aggs)
+    if (a.kind != CAPF_AGG_COUNT_STAR) return false;
+  Session *s = grp->s;
+  // the keys below the projections of the RETURN items (column copies and
+  // literals), then through the join tree: a column of a leaf, or a literal
+  std::vector<TCol> gk;
+  for (int k : grp->key_index) gk.push_back(TCol{k, nullptr});
+  const NodePtr n = through_mappings(grp->kids[0], gk);
+  for (NodePtr x = grp->kids[0];; x = x->kids[0]) {
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->result) return false;  // already materialised: the plain group is cheap
+    if (x == n) break;
+  }
+  JoinGraph g;
+  std::vector<ColRef> cols;
+  if (!collect(n, g, cols)) return false;
+  if (g.eqs.empty()) return false;  // no join: nothing to fuse
+  if (g.neqs.size() > 4) return false;
+  const size_t nk = gk.size();
+  std::vector<int> kcol(nk, -1);                   // the key's column of G, or
+  std::vector<const Program *> klit(nk, nullptr);  // its literal
+  int G = -1;
+  for (size_t i = 0; i < nk; ++i) {
+    if (gk[i].lit) {
+      klit[i] = gk[i].lit;
+      continue;
+    }
+    const ColRef &r = cols[(size_t)gk[i].col];
+    if (r.leaf >= 0) {
+      if (G >= 0 && G != r.leaf) return false;  // keys of two leaves
+      G = r.leaf;
+      kcol[i] = r.col;
+    } else if (r.leaf == -2 && r.col >= 0) {
+      klit[i] = &g.lits[(size_t)r.col];
+    } else {
+      return false;
+    }
+  }
+  if (G < 0) return false;
+  for (auto &ne : g.neqs)
+    if (ne.first.leaf == G || ne.second.leaf == G) return false;
+  const int k = (int)g.neqs.size();
+  std::vector<JoinGraph> terms(1 << k);
+  std::vector<int> root(1 << k, G);
+  for (int mask = 0; mask < (1 << k); ++mask) {
+    std::vector<int> subset;
+    for (int b = 0; b < k; ++b)
+      if (mask >> b & 1) subset.push_back(b);
+    if (!apply_equalities(g, subset, terms[mask], &root[mask])) return false;
+    // G keeps its rows only while no term filters or contracts it
+    if (root[mask] < 0 || !terms[mask].leaves[root[mask]].col_eqs.empty()) return false;
+  }
+  RowsOut ro;
+  ro.data = leaf_data(g.leaves[G]);
+  const Data &gd = *ro.data.data;
+  const int64_t nrows = gd.nrows;
+  if (nrows >= (int64_t(1) << 40)) return false;
+  ColPtr weight = make_column(s, Type::Int64, nrows, false);
+  ro.acc = nrows > 0 ? (unsigned long long *)weight->data->p : nullptr;  // (no rows: no buffer, no launch)
+  std::string detail;
+  for (int mask = 0; mask < (1 << k); ++mask) {
+    if (mask) detail += '|';
+    ro.root = root[mask];
+    ro.mode = mask == 0 ? ROWS_SET : (__builtin_popcount(mask) & 1) ? ROWS_SUB : ROWS_ADD;
+    if (!tree_count(s, terms[mask], nullptr, detail, &ro)) {
+      s->sync();  // kernels of earlier terms may still read their maps
+      return false;
+    }
+  }
+  // the rows with joined rows
+  int64_t m = 0;
+  BufPtr idx;  // null: G has no rows (identity gathers)
+  if (nrows > 0) {
+    BufPtr flags = s->alloc(nrows);
+    hipLaunchKernelGGL(k_rows_nonzero, dim3(grid_for(nrows, 256)), dim3(256), 0, s->stream,
+                       (const unsigned long long *)ro.acc, nrows, (uint8_t *)flags->p);
+    KERNEL_CHECK();
+    idx = compact_flags(s, (const uint8_t *)flags->p, nrows, &m);
+  }
+  bool unique = false;
+  for (size_t i = 0; i < nk && !unique; ++i) {
+    if (kcol[i] < 0) continue;
+    const Type t = g.leaves[G].node->types[(size_t)kcol[i]];
+    if (t == Type::List || t == Type::Null) continue;
+    unique = column_unique(g.leaves[G].node, kcol[i]);
+  }
+  auto literal = [&](size_t i, int64_t rows) {
+    Data e;
+    e.nrows = rows;
+    return eval_program(s, *klit[i], {}, e, grp->types[i]);
+  };
+  IdxCache cache;
+  auto out = std::make_shared<Data>();
+  if (unique) {
+    out->nrows = m;
+    for (size_t i = 0; i < nk; ++i)
+      out->cols.push_back(kcol[i] >= 0 ? gather_lazy(s, gd.cols[(size_t)kcol[i]], idx, m, false, &cache)
+                                       : literal(i, m));
+    ColPtr cnt = idx ? gather_column(s, weight, (const int64_t *)idx->p, m) : weight;
+    for (size_t a = 0; a < grp->aggs.size(); ++a) out->cols.push_back(cnt);
+  } else {
+    Data t;  // (G's key columns, weight) of the surviving rows
+    t.nrows = m;
+    std::vector<int> keys, at(nk, -1);
+    for (size_t i = 0; i < nk; ++i) {
+      if (kcol[i] < 0) continue;
+      at[i] = (int)t.cols.size();
+      keys.push_back(at[i]);
+      t.cols.push_back(gather_lazy(s, gd.cols[(size_t)kcol[i]], idx, m, false, &cache));
+    }
+    ColPtr w = idx ? gather_column(s, weight, (const int64_t *)idx->p, m) : weight;
+    Grouping gr = group_rows(s, t, keys);
+    out->nrows = gr.ngroups;
+    for (size_t i = 0; i < nk; ++i)
+      out->cols.push_back(at[i] >= 0 ? gather_column(s, t.cols[(size_t)at[i]], (const int64_t *)gr.rep_row->p, gr.ngroups)
+                                     : literal(i, gr.ngroups));
+    ColPtr cnt = aggregate(s, gr, t, m, CAPF_AGG_SUM, w, Type::Int64);
+    for (size_t a = 0; a < grp->aggs.size(); ++a) out->cols.push_back(cnt);
+  }
+  s->last_plan = "message_passing_grouped";
+  s->last_plan_detail = detail + (unique ? " group:unique" : " group:hash");
+  result = out;
   return true;
 }
 

@@ -38,6 +38,17 @@ struct LeafData {
   bool plain = false;  // unfiltered base data (eligible for column stats / merges)
 };
 
+// A tracked column of a plan node: its index, or the literal it was set to.
+struct TCol {
+  int col = -1;
+  const Program *lit = nullptr;
+};
+
+// Descends through column-mapping operators (Select; withColumns whose
+// expressions are column copies or literals), re-expressing the tracked
+// columns; returns the first other node (reach_plan.hip).
+NodePtr through_mappings(NodePtr n, std::vector<TCol> &cols);
+
 // The join graph below n and, per column of n, where it comes from; false: an
 // operator or key type the fused paths do not read.
 bool collect(const NodePtr &n, JoinGraph &g, std::vector<ColRef> &out);

@@ -49,12 +49,6 @@ static bool progs_eq(const std::vector<Program> &a, const std::vector<Program> &
   return true;
 }
 
-// A tracked column: index in the current node, or a literal.
-struct TCol {
-  int col = -1;
-  const Program *lit = nullptr;
-};
-
 static bool reach_reject(const char *why) {
   static const bool trace = getenv("CAPF_TRACE_FUSE") && atoi(getenv("CAPF_TRACE_FUSE")) == 1;
   if (trace) fprintf(stderr, "[capf] fused reach not applied: %s\n", why);
@@ -72,7 +66,7 @@ static bool is_literal_program(const Program &p) { return p.code.size() == 1 && 
 // Descends through column-mapping operators (Select; withColumns whose
 // expressions are column copies or literals), re-expressing the tracked
 // columns; returns the first other node.
-static NodePtr through_mappings(NodePtr n, std::vector<TCol> &cols) {
+NodePtr through_mappings(NodePtr n, std::vector<TCol> &cols) {
   for (;;) {
     if (n->kind == Kind::Select) {
       for (auto &c : cols)

@@ -661,6 +661,8 @@ static DataPtr materialize_impl(const NodePtr &n) {
       if (!n->key_index.empty()) {
         DataPtr fused;
         if (try_fused_reach(n, fused)) return fused;
+        // group(keys of one leaf; count(*)) over an inner-join tree: per-row weights
+        if (try_fused_group_count(n, fused)) return fused;
       }
       // fused factorised count: group(∅, count(*)) over an inner-join tree
       bool all_count_star = n->key_index.empty() && !n->aggs.empty();

@@ -337,11 +337,16 @@ capf_status capf_session_profile_count(capf_session *s, int32_t *n);
 capf_status capf_session_profile_entry(capf_session *s, int32_t i, const char **kernel,
                                        int64_t *launches, double *total_ms, double *bytes);
 /* last fused execution path taken ("fused_chain2", "fused_triangle", "message_passing",
+ * "message_passing_grouped" (group(keys of one leaf; count(*)) over an inner-join tree:
+ * that leaf is the root and keeps one weight per row),
  * "fused_var_length_reach" (lower bound 0 / 1: BFS), "fused_var_length_trails"
  * (lower bound >= 2: trail enumeration), "fused_var_length_undirected" (undirected
  * pattern: step enumeration); "none" until one runs) */
 const char *capf_session_last_plan(capf_session *s);
-/* the messages and root kernel of the last "message_passing" count (DESIGN.md "Plan detail"); "" until one runs */
+/* the messages and root kernel of the last "message_passing" count (DESIGN.md "Plan detail"); "" until one runs.
+ * "message_passing_grouped" uses the same grammar per term with the root token "rows:<nchild>",
+ * "rows1:<kind>:w<3|4|8>" or "rows_all", and ends in " group:unique" (every surviving row of the
+ * group leaf is its own group) or " group:hash" (the rows are grouped, their weights summed) */
 const char *capf_session_last_plan_detail(capf_session *s);
 
 /* String dictionary for CAPF_TYPE_STRING columns. */
